@@ -1,16 +1,20 @@
 #!/usr/bin/env python
 """Benchmark of the MI355X-native Balanced Group Softmax hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gs_head]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gs_head] [--dump-outputs DIR] [--full]
 
 Contract: W untimed warm-up steps, then exactly K timed steps bracketed by barrier +
 ``torch.cuda.synchronize()``; the MAX over ranks is taken and rank 0 prints ONE JSON line.
+A plain run does only what that headline needs (set-up, the launch-policy calibration, warm-up, the K timed steps).
+``--dump-outputs DIR`` writes what the last timed step handed its caller as ``DIR/<name>.npy`` (fixed, seeded inputs:
+two builds compare output for output).  ``--full`` adds the secondary measurements below (rooflines, the other
+configurations, the CPU baselines, the N > 1 diagnostics).
 
 Workload ``gs_head`` (this round): the RoI-head loss of BASELINE.json config[1]
 (Faster R-CNN R50-FPN + BAGS, 2 img/GPU x 512 RoI = 1024 RoIs x 1236 logits, 25 % fg):
 one step = ``_remap_labels`` (device sampling) + fused GroupSoftmax loss forward+backward
 (+ the reduce / scale kernels) + the box-regression loss, inputs resident in HBM.
-The JSON line carries ``roofline`` for the dominant kernel (the fused streaming kernel,
+With ``--full`` the JSON line carries ``roofline`` for the dominant kernel (the fused streaming kernel,
 HIP-event timed on its own stream) and ``cpu_baseline`` = the torch-CPU port of the
 reference's loss()+backward() timed on this host (rank 0, N=1 only).
 """
@@ -78,6 +82,14 @@ def parse():
                          "operands, fp32-faithful), 'f32' (v_mfma_f32_32x32x2_f32) or 'bf16' (operands "
                          "rounded to bf16, fp32 accumulate: the reduced-precision mode of cfg[4])")
     ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the secondary measurements: per-kernel rooflines, the other configurations, the CPU '
+                         'baselines, the N > 1 diagnostics, the eager figure beside a timed hipGraph (the --no-* '
+                         'options above trim them)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (losses, trainable '
+                         'parameters after the update and their gradients; gs_head: losses and the logits gradient) '
+                         'as DIR/<name>.npy, float32, at most 64 MB in all')
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
     a = ap.parse_args()
     if a.conv_math is not None:
@@ -192,6 +204,8 @@ def run_graph_child(args):
     cmd += ['--htc'] if args.htc else []
     cmd += ['--dist-graph'] if args.dist_graph else []
     cmd += ['--launch', args.launch]
+    cmd += ['--full'] if args.full else []
+    cmd += ['--dump-outputs', args.dump_outputs] if args.dump_outputs else []
     try:
         out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
         line = [ln for ln in out.stdout.decode().splitlines() if ln.startswith('{')]
@@ -204,8 +218,60 @@ def run_graph_child(args):
     return None
 
 
+DUMP_BYTES = 64 << 20
+
+
+def write_outputs(dirname, arrays):
+    """``arrays``: (name, tensor) pairs -> ``dirname/<name>.npy`` in float32 (float64 data stays float64).  Over
+    DUMP_BYTES in all, every array above a common cap is cut to a fixed, seeded sample of that many of its flattened
+    elements (the same indices for the same size), so that two builds still compare element for element."""
+    os.makedirs(dirname, exist_ok=True)
+    host = []
+    for name, t in arrays:
+        t = torch.as_tensor(t).detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        host.append((name, t.cpu().numpy()))
+    budget = DUMP_BYTES - 256 * len(host)                  # (room for the .npy headers)
+    cap = max([a.nbytes for _, a in host] + [0])
+    if sum(a.nbytes for _, a in host) > budget:
+        sizes = sorted(a.nbytes for _, a in host)
+        rest = budget
+        for i, nb in enumerate(sizes):
+            if nb * (len(sizes) - i) > rest:
+                cap = rest // (len(sizes) - i)
+                break
+            rest -= nb
+    for name, a in host:
+        flat = a.reshape(-1)
+        keep = cap // a.itemsize
+        if flat.size > keep:
+            a = flat[np.sort(np.random.default_rng(0).choice(flat.size, keep, replace=False))]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
+def detector_outputs(step):
+    """What one training iteration hands its caller: the logged losses, the trainable parameters after the optimizer
+    step and the gradients it applied."""
+    arrays = [('loss.' + k, v) for k, v in sorted(step.last.items())]
+    names = {id(p): n for n, p in step.model.named_parameters()}
+    for i, p in enumerate(step.params):
+        n = names.get(id(p), 'param%d' % i)
+        arrays.append(('param.' + n, p))
+        if p.grad is not None:
+            arrays.append(('grad.' + n, p.grad))
+    return arrays
+
+
 def finish_line(out, args, dev, world):
-    """Secondary measurements + per-kernel rooflines + CPU baseline, then the ONE JSON line."""
+    """With --full: secondary measurements + per-kernel rooflines + CPU baseline; then the ONE JSON line."""
+    if args.full:
+        full_measurements(out, args, dev, world)
+    print(json.dumps(out), flush=True)
+
+
+def full_measurements(out, args, dev, world):
+    """The secondary fields of the line (``--full``): every one runs after the timed region and leaves the headline
+    fields as they are."""
     # (per-kernel rooflines first, the other configurations after them; every measurement here is standalone)
     run_extras = world == 1 and not args.no_extras and args.selectp == 1 and not args.mask \
         and not args.cascade and not args.htc
@@ -250,7 +316,6 @@ def finish_line(out, args, dev, world):
         cbd = cpu_baseline_detector()
         if cbd:
             out['cpu_baseline_detector'] = cbd
-    print(json.dumps(out), flush=True)
 
 
 def run_dist_graph_children(args, rank, local, world):
@@ -386,6 +451,8 @@ def main_detector_dist(args, rank, local, world, dev, step, dist_graph):
                 out['ms_per_step_eager'] = calib['eager_forks_on_ms']
         for k, v in (f.get('diagnostics') or {}).items():
             out[k] = v
+        if 'dump_outputs_error' in f:
+            out['dump_outputs'] = f['dump_outputs_error']
         if dist_graph is not None:
             out['dist_graph_policy'] = dist_graph
         if f.get('watchdog'):
@@ -395,8 +462,13 @@ def main_detector_dist(args, rank, local, world, dev, step, dist_graph):
             return
         finish_line(out, args, dev, world)
 
+    after_timed = None
+    if args.dump_outputs and rank == 0:
+        def after_timed():
+            write_outputs(args.dump_outputs, detector_outputs(step))
     bench_dist.run(step, args, rank, world, make_one_rank_step, emit,
-                   launch_auto=args.launch == 'auto' and not os.environ.get('BGS_BENCH_NO_DIST_CALIB'))
+                   launch_auto=args.launch == 'auto' and not os.environ.get('BGS_BENCH_NO_DIST_CALIB'),
+                   after_timed=after_timed)
 
 
 def main_detector(args, rank, local, world, dev):
@@ -483,6 +555,8 @@ def main_detector(args, rank, local, world, dev):
     if pipelined:
         fn.drain()                             # (the features launched by the last timed call: consumed by nobody)
         torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, detector_outputs(step))
     ms_per_step = dt * 1e3 / args.steps
     imgs_per_s = args.imgs * world * args.steps / dt
     rank_ms = None
@@ -495,7 +569,7 @@ def main_detector(args, rank, local, world, dev):
         graph = None                           # (the line's `launch` describes what was timed)
     if pipelined:
         ms_eager = (calib or {}).get('eager_ms')
-    elif graph is not None:     # every rank: the same step launched eagerly, for the graph-vs-eager figure
+    elif graph is not None and args.full:     # every rank: the same step launched eagerly, for the graph-vs-eager figure
         ms_eager = round(timed_loop(step, 5, 2, world) * 1e3 / 5, 3)
     if rank == 0:
         out = detector_line(args, step, world, imgs_per_s, ms_per_step, graph, pipelined,
@@ -559,13 +633,16 @@ def main():
     graph = None if args.no_graph else try_graph(step)
     fn = graph.replay if graph is not None else step
     dt = timed_loop(fn, args.steps, args.warmup, world)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, [('loss', step.total), ('loss_terms', step.terms),
+                                          ('logits_grad', step.logits.grad)])
     ms_per_step = dt * 1e3 / args.steps
     us_per_roi = dt * 1e6 / (args.steps * n * world)
 
     if rank == 0:
         # eager (python launch overhead included) for reference
         dt_eager = None
-        if graph is not None and world == 1:
+        if graph is not None and world == 1 and args.full:
             dt_eager = timed_loop(step, min(args.steps, 100), 5, 1) * 1e3 / min(args.steps, 100)
         out = {
             'metric': 'GroupSoftmax us/RoI (loss fwd+bwd; BASELINE metric: img/s/GPU fwd+bwd '
@@ -585,12 +662,13 @@ def main():
         }
         if dt_eager is not None:
             out['ms_per_step_eager'] = round(dt_eager, 5)
-        out['roofline'] = kernel_roofline(inp, n, kernel='fused' if n <= BF.GS_FUSED_MAX_ROWS else 'rowwave')
-        out['roofline_rowwave'] = kernel_roofline(inp, n, kernel='rowwave')
-        big = make_inputs(65536, seed=7, dev=dev)
-        out['roofline_n65536'] = kernel_roofline(big, 65536, iters=30, kernel='rowwave')
-        del big
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out['roofline'] = kernel_roofline(inp, n, kernel='fused' if n <= BF.GS_FUSED_MAX_ROWS else 'rowwave')
+            out['roofline_rowwave'] = kernel_roofline(inp, n, kernel='rowwave')
+            big = make_inputs(65536, seed=7, dev=dev)
+            out['roofline_n65536'] = kernel_roofline(big, 65536, iters=30, kernel='rowwave')
+            del big
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(n, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     barrier(world)

@@ -320,10 +320,12 @@ def n1_reference(make_one_rank_step, steps, warmup, rank, world, ms_per_step_n, 
     return out
 
 
-def run(step, args, rank, world, make_one_rank_step, emit, launch_auto=True):
+def run(step, args, rank, world, make_one_rank_step, emit, launch_auto=True, after_timed=None):
     """Everything bench.py does for N > 1 between the model build and the JSON line.  ``emit(fields)`` is called exactly
     once, on rank 0, with: ms_per_step, dt, pipelined depth, per-rank times, launch calibration, the diagnostics —
-    from the main thread when all went well, from the watchdog thread with what exists when a phase ran out of time."""
+    from the main thread when all went well, from the watchdog thread with what exists when a phase ran out of time.
+    The diagnostics run only with ``args.full`` (bench.py --full); ``after_timed()`` is called right after the timed
+    steps, before any other GPU work (bench.py --dump-outputs)."""
     state = dict(fields=None, emitted=False)
     lock = threading.Lock()
 
@@ -355,13 +357,18 @@ def run(step, args, rank, world, make_one_rank_step, emit, launch_auto=True):
     fields = dict(dt=dt, ms_per_step=ms_per_step, pipeline_depth=depth, rank_ms=rank_ms, launch_calibration=calib,
                   step_fn=fn, diagnostics={})
     state['fields'] = fields
+    if after_timed is not None:
+        try:
+            after_timed()
+        except Exception as e:      # the headline above is already safe: the failure becomes a field of its own
+            fields['dump_outputs_error'] = _err(e)
     # ---- diagnostics: bounded, each one guarded; the headline above is already safe
     state['phase'] = 'diagnostics'
     budget = float(os.environ.get('BGS_BENCH_DIAG_SECONDS', '90'))
     wd = Watchdog(budget, lambda: emit_once(dict(watchdog='diagnostics exceeded %.0f s (%s unfinished)'
                                                          % (budget, state.get('diag', '?')))), code=0)
     diag = fields['diagnostics']
-    if not os.environ.get('BGS_BENCH_NO_DIAG'):
+    if getattr(args, 'full', False) and not os.environ.get('BGS_BENCH_NO_DIAG'):
         state['diag'] = 'grad_exchange_check'
         diag['grad_exchange_check'] = exchange_check(step, world, rank)
         state['diag'] = 'allreduce_us'

@@ -60,16 +60,19 @@ class GsHeadStep(object):
         # other ones tensor — the scaling launch runs and finds out on the device that every factor is 1
         dev = inp['logits'].device
         self.one = BF.unit_gradient(dev) if unit_root else torch.ones(1, dtype=torch.float32, device=dev)
+        self.terms = self.total = None          # the last call's loss terms and their sum (bench.py --dump-outputs)
 
     def __call__(self):
         i = self.inp
         self.logits.grad = None
-        _terms, total, _avg = BF.gs_head_step(self.logits, i['labels'], i['l2b'], i['ps_np'], 8.0, 12345,
+        self.terms, total, _avg = BF.gs_head_step(self.logits, i['labels'], i['l2b'], i['ps_np'], 8.0, 12345,
                                               draw_counter=self.draw, bbox_pred=i['bbox_pred'],
                                               bbox_targets=i['bbox_targets'],
                                               bbox_weights=i['bbox_weights'],
                                               num_reg_classes=NUM_CLASSES, beta=1.0, box_loss_weight=1.0)
         total.backward(self.one)
+        # detached: holding the loss would keep this call's autograd graph alive until the next call
+        self.terms, self.total = self.terms.detach(), total.detach()
         return total
 
 

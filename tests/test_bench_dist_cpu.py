@@ -15,8 +15,8 @@ import bench_dist_dryrun as dry  # noqa: E402
 WORLD = 8
 
 
-def _run(env, port_off):
-    lines, wall, ok = dry.run_scenario(env, WORLD, port=37000 + port_off + os.getpid() % 1500)
+def _run(env, port_off, full=True):
+    lines, wall, ok = dry.run_scenario(env, WORLD, port=37000 + port_off + os.getpid() % 1500, full=full)
     assert ok, 'a rank left with a non-zero exit code'
     assert len(lines) == 1, lines
     return lines[0], wall
@@ -36,6 +36,13 @@ def test_clean_run_measures_everything():
     assert isinstance(d['allreduce_us'], float) and d['allreduce_us'] > 0
     assert d['n1_same_invocation']['ms_per_step'] > 0 and d['weak_scaling_eff'] > 0
     assert set(f['launch_calibration']['ms_by_rank']) == {'forks_on', 'pipelined'}      # the default arms only
+    assert wall < 60
+
+
+def test_a_plain_run_times_the_headline_without_the_diagnostics():
+    f, wall = _run({}, 5, full=False)
+    _headline_ok(f)
+    assert f['diagnostics'] == {}
     assert wall < 60
 
 

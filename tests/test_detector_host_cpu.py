@@ -1,8 +1,6 @@
 """CPU: host-side detector logic (assignment, sampling, anchors, module/state-dict layout)
 checked against the REFERENCE's own classes executed on CPU through the import stubs
-(oracle/ref_import.py).  Skipped where the reference tree is absent (GPU box)."""
-import os
-
+(oracle/ref_import.py); where the reference tree is absent their recorded outputs stand in (tests/reference_record.py)."""
 import numpy as np
 import pytest
 import torch
@@ -12,9 +10,7 @@ from oracle import tensor_forms as A
 from balancedgroupsoftmax_amd import rpn as R
 from balancedgroupsoftmax_amd.config import to_config_dict
 from oracle import ref_import
-
-needs_ref = pytest.mark.skipif(not ref_import.reference_available(),
-                               reason='reference tree not present')
+from tests import reference_record as RR
 
 
 def rand_boxes(n, seed, size=400):
@@ -32,43 +28,52 @@ def test_anchor_generator_known_answer():
                             [16., 16., 24., 24.]]
 
 
-@needs_ref
 def test_anchor_generator_vs_reference():
-    ref_import.install_stubs()
-    from mmdet.core.anchor.anchor_generator import AnchorGenerator as Ref
     for base, fs, st in [(4, (7, 9), 4), (32, (5, 3), 32), (64, (13, 21), 64)]:
-        mine, ref = R.AnchorGenerator(base, [8], [0.5, 1.0, 2.0]), Ref(base, [8], [0.5, 1.0, 2.0])
-        assert torch.equal(mine.base_anchors, ref.base_anchors)
-        assert torch.equal(mine.grid_anchors(fs, st, 'cpu'), ref.grid_anchors(fs, st, 'cpu'))
+        def compute():
+            ref_import.install_stubs()
+            from mmdet.core.anchor.anchor_generator import AnchorGenerator as Ref
+            ref = Ref(base, [8], [0.5, 1.0, 2.0])
+            return dict(base=ref.base_anchors, grid=ref.grid_anchors(fs, st, 'cpu'),
+                        valid=ref.valid_flags(fs, (fs[0] - 1, fs[1] - 2), 'cpu').bool())
+        ref = RR.arrays('anchor_generator/%d_%d_%d_%d' % (base, fs[0], fs[1], st), compute)
+        mine = R.AnchorGenerator(base, [8], [0.5, 1.0, 2.0])
+        assert torch.equal(mine.base_anchors, torch.from_numpy(ref['base']))
+        assert torch.equal(mine.grid_anchors(fs, st, 'cpu'), torch.from_numpy(ref['grid']))
         v = mine.valid_flags(fs, (fs[0] - 1, fs[1] - 2), 'cpu')
-        assert torch.equal(v, ref.valid_flags(fs, (fs[0] - 1, fs[1] - 2), 'cpu').bool())
+        assert torch.equal(v, torch.from_numpy(ref['valid']))
 
 
-@needs_ref
 def test_bbox_overlaps_vs_reference():
-    ref_import.install_stubs()
-    from mmdet.core.bbox.geometry import bbox_overlaps as ref
     a, b = rand_boxes(37, 0), rand_boxes(211, 1)
-    assert torch.equal(A.bbox_overlaps(a, b), ref(a, b))
+
+    def compute():
+        ref_import.install_stubs()
+        from mmdet.core.bbox.geometry import bbox_overlaps as ref
+        return dict(iou=ref(a, b))
+    assert torch.equal(A.bbox_overlaps(a, b), torch.from_numpy(RR.arrays('bbox_overlaps', compute)['iou']))
 
 
-@needs_ref
 @pytest.mark.parametrize('thr', [(0.7, 0.3, 0.3), (0.5, 0.5, 0.5)])
 def test_max_iou_assigner_vs_reference(thr):
-    ref_import.install_stubs()
-    from mmdet.core.bbox.assigners.max_iou_assigner import MaxIoUAssigner
     pos, neg, minpos = thr
-    ref = MaxIoUAssigner(pos_iou_thr=pos, neg_iou_thr=neg, min_pos_iou=minpos, ignore_iof_thr=-1)
     for seed in range(5):
         gts, boxes = rand_boxes(23, seed), rand_boxes(3000, 100 + seed)
         boxes[:40] = gts[torch.arange(40) % 23] + torch.randn(40, 4, generator=torch.Generator(
         ).manual_seed(seed)) * 2            # near-duplicates: real positives
         boxes[40:46] = boxes[:6]            # exact ties between boxes for the same gt (step 4)
         ov = A.bbox_overlaps(gts, boxes)
-        exp = ref.assign_wrt_overlaps(ov.clone())
+
+        def compute():
+            ref_import.install_stubs()
+            from mmdet.core.bbox.assigners.max_iou_assigner import MaxIoUAssigner
+            ref = MaxIoUAssigner(pos_iou_thr=pos, neg_iou_thr=neg, min_pos_iou=minpos, ignore_iof_thr=-1)
+            exp = ref.assign_wrt_overlaps(ov.clone())
+            return dict(gt_inds=exp.gt_inds, max_overlaps=exp.max_overlaps)
+        exp = RR.arrays('max_iou_assigner/%g_%g_%g/%d' % (pos, neg, minpos, seed), compute)
         got, mx = A.max_iou_assign(ov, pos, neg, minpos)
-        assert torch.equal(got, exp.gt_inds)
-        assert torch.equal(mx, exp.max_overlaps)
+        assert torch.equal(got, torch.from_numpy(exp['gt_inds']))
+        assert torch.equal(mx, torch.from_numpy(exp['max_overlaps']))
         assert (got > 0).sum() > 20 and (got == 0).sum() > 100
 
 
@@ -110,12 +115,9 @@ def _rpn_cfg(num):
         allowed_border=0, pos_weight=-1, debug=False))
 
 
-@needs_ref
 def test_rpn_anchor_targets_vs_reference():
     """With a sampler budget larger than the anchor count nothing is dropped, so the dense
     targets are deterministic and must equal the reference's anchor_target_single."""
-    ref_import.install_stubs()
-    from mmdet.core.anchor.anchor_target import anchor_target_single
     head = bgs.build_head(dict(type='RPNHead', in_channels=16, feat_channels=16,
                                anchor_scales=[8], anchor_ratios=[0.5, 1.0, 2.0],
                                anchor_strides=[4, 8, 16, 32, 64]))
@@ -128,54 +130,59 @@ def test_rpn_anchor_targets_vs_reference():
     cfg = _rpn_cfg(num=10 ** 7)
     labels, lw, bt, bw, npos, nneg = A.rpn_anchor_targets(head, anchors, valid, gts,
                                                           meta['img_shape'], cfg)
-    np.random.seed(0)
-    exp = anchor_target_single(anchors, valid.to(torch.uint8), gts, None, None, meta,
-                               head.target_means, head.target_stds, cfg, sampling=True)
-    assert torch.equal(labels, exp[0]) and torch.equal(lw, exp[1])
-    assert torch.allclose(bt, exp[2], atol=1e-6) and torch.equal(bw, exp[3])
-    assert int(npos) == exp[4].numel() and int(nneg) == exp[5].numel() and int(npos) > 4
+
+    def compute():
+        ref_import.install_stubs()
+        from mmdet.core.anchor.anchor_target import anchor_target_single
+        np.random.seed(0)
+        e = anchor_target_single(anchors, valid.to(torch.uint8), gts, None, None, meta,
+                                 head.target_means, head.target_stds, cfg, sampling=True)
+        return dict(labels=e[0], label_weights=e[1], bbox_targets=e[2], bbox_weights=e[3],
+                    num_pos=np.int64(e[4].numel()), num_neg=np.int64(e[5].numel()))
+    exp = {k: torch.from_numpy(np.asarray(v)) for k, v in RR.arrays('rpn_anchor_targets', compute).items()}
+    assert torch.equal(labels, exp['labels']) and torch.equal(lw, exp['label_weights'])
+    assert torch.allclose(bt, exp['bbox_targets'], atol=1e-6) and torch.equal(bw, exp['bbox_weights'])
+    assert int(npos) == int(exp['num_pos']) and int(nneg) == int(exp['num_neg']) and int(npos) > 4
 
 
 REF_KEYS = {}
 
 
-@needs_ref
 def test_state_dict_layout_matches_reference_modules():
     """Checkpoint compatibility surface: parameter/buffer names AND shapes of
     ResNet-50, FPN and RPNHead equal those of the reference's own modules."""
-    ref_import.install_stubs()
-    from mmdet.models.anchor_heads.rpn_head import RPNHead as RefRPN
-    from mmdet.models.backbones.resnet import ResNet as RefResNet
-    from mmdet.models.necks.fpn import FPN as RefFPN
-
-    def sig(m):
-        return {k: tuple(v.shape) for k, v in m.state_dict().items()}
-
-    mine = bgs.build_backbone(dict(type='ResNet', depth=50, num_stages=4,
-                                   out_indices=(0, 1, 2, 3), frozen_stages=1, style='pytorch'))
-    ref = RefResNet(depth=50, num_stages=4, out_indices=(0, 1, 2, 3), frozen_stages=1,
-                    style='pytorch')
-    assert sig(mine) == sig(ref)
-    assert [n for n, p in mine.named_parameters() if not p.requires_grad] == \
-        [n for n, p in ref.named_parameters() if not p.requires_grad]      # frozen_stages=1
-    neck = dict(type='FPN', in_channels=[256, 512, 1024, 2048], out_channels=256, num_outs=5)
-    assert sig(bgs.build_neck(neck)) == sig(RefFPN(in_channels=[256, 512, 1024, 2048],
-                                                   out_channels=256, num_outs=5))
     rpn = dict(in_channels=256, feat_channels=256, anchor_scales=[8],
                anchor_ratios=[0.5, 1.0, 2.0], anchor_strides=[4, 8, 16, 32, 64],
                target_means=[.0, .0, .0, .0], target_stds=[1.0, 1.0, 1.0, 1.0],
                loss_cls=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0),
                loss_bbox=dict(type='SmoothL1Loss', beta=1.0 / 9.0, loss_weight=1.0))
-    assert sig(bgs.build_head(dict(type='RPNHead', **rpn))) == sig(RefRPN(**rpn))
+
+    def compute():
+        ref_import.install_stubs()
+        from mmdet.models.anchor_heads.rpn_head import RPNHead as RefRPN
+        from mmdet.models.backbones.resnet import ResNet as RefResNet
+        from mmdet.models.necks.fpn import FPN as RefFPN
+        ref = RefResNet(depth=50, num_stages=4, out_indices=(0, 1, 2, 3), frozen_stages=1,
+                        style='pytorch')
+        return dict(resnet=RR.signature(ref),
+                    resnet_frozen=[n for n, p in ref.named_parameters() if not p.requires_grad],
+                    fpn=RR.signature(RefFPN(in_channels=[256, 512, 1024, 2048], out_channels=256, num_outs=5)),
+                    rpn=RR.signature(RefRPN(**rpn)))
+    ref = RR.value('state_dict_layout/r50_fpn_rpn', compute)
+    mine = bgs.build_backbone(dict(type='ResNet', depth=50, num_stages=4,
+                                   out_indices=(0, 1, 2, 3), frozen_stages=1, style='pytorch'))
+    assert RR.signature(mine) == ref['resnet']
+    assert [n for n, p in mine.named_parameters() if not p.requires_grad] == ref['resnet_frozen']  # frozen_stages=1
+    neck = dict(type='FPN', in_channels=[256, 512, 1024, 2048], out_channels=256, num_outs=5)
+    assert RR.signature(bgs.build_neck(neck)) == ref['fpn']
+    assert RR.signature(bgs.build_head(dict(type='RPNHead', **rpn))) == ref['rpn']
 
 
-@needs_ref
 def test_full_detector_builds_from_reference_config(tmp_path):
     """configs/bags/gs_faster_rcnn_r50_fpn_1x_lvis_with0_bg8.py drops in: only the three data
     file paths (absent from the repo, README.md:83-87) are redirected to synthetic tables."""
     from balancedgroupsoftmax_amd import gs_tables, train
-    cfg = bgs.Config.fromfile(os.path.join(
-        ref_import.REFERENCE_ROOT, 'configs/bags/gs_faster_rcnn_r50_fpn_1x_lvis_with0_bg8.py'))
+    cfg = RR.config('configs/bags/gs_faster_rcnn_r50_fpn_1x_lvis_with0_bg8.py')
     paths = gs_tables.save_group_tables(str(tmp_path), *gs_tables.synthetic_group_tables())
     gs = cfg.model.bbox_head.gs_config
     gs.label2binlabel, gs.pred_slice, gs.fg_split = (paths['label2binlabel'], paths['pred_slice'],

@@ -14,6 +14,7 @@ import torch
 import balancedgroupsoftmax_amd as bgs
 from balancedgroupsoftmax_amd import checkpoint, gs_tables
 from oracle import ref_import
+from tests import reference_record as RR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -99,30 +100,34 @@ def test_checkpoint_roundtrip_and_mmcv_layout(tmp_path):
         checkpoint.load_checkpoint(other, path, strict=True)
 
 
-@pytest.mark.skipif(not ref_import.reference_available(), reason='reference tree absent')
 def test_reference_module_checkpoint_loads_into_the_detector(tmp_path):
     """A checkpoint written from the REFERENCE's own modules (ResNet-50 + FPN + RPNHead, the
     'pretrained Faster R-CNN' BAGS starts from) loads key-for-key; only the 1231-row fc_cls of a
     plain head mismatches the 1236-row BAGS head — what the reference re-initialises, too."""
-    ref_import.install_stubs()
-    from mmdet.models.anchor_heads.rpn_head import RPNHead as RefRPN
-    from mmdet.models.backbones.resnet import ResNet as RefResNet
-    from mmdet.models.necks.fpn import FPN as RefFPN
-    sd = collections.OrderedDict()
-    for prefix, m in (('backbone', RefResNet(depth=50, num_stages=4, out_indices=(0, 1, 2, 3),
-                                            frozen_stages=1, style='pytorch')),
-                      ('neck', RefFPN(in_channels=[256, 512, 1024, 2048], out_channels=256, num_outs=5)),
-                      ('rpn_head', RefRPN(in_channels=256, feat_channels=256, anchor_scales=[8],
-                                          anchor_ratios=[0.5, 1.0, 2.0],
-                                          anchor_strides=[4, 8, 16, 32, 64]))):
-        for k, v in m.state_dict().items():
-            sd['%s.%s' % (prefix, k)] = v
+    def compute():
+        ref_import.install_stubs()
+        from mmdet.models.anchor_heads.rpn_head import RPNHead as RefRPN
+        from mmdet.models.backbones.resnet import ResNet as RefResNet
+        from mmdet.models.necks.fpn import FPN as RefFPN
+        out = {}
+        for prefix, m in (('backbone', RefResNet(depth=50, num_stages=4, out_indices=(0, 1, 2, 3),
+                                                frozen_stages=1, style='pytorch')),
+                          ('neck', RefFPN(in_channels=[256, 512, 1024, 2048], out_channels=256, num_outs=5)),
+                          ('rpn_head', RefRPN(in_channels=256, feat_channels=256, anchor_scales=[8],
+                                              anchor_ratios=[0.5, 1.0, 2.0],
+                                              anchor_strides=[4, 8, 16, 32, 64]))):
+            for k, shape in RR.signature(m).items():
+                out['%s.%s' % (prefix, k)] = shape
+        return out
+    # the reference modules' keys and shapes (recorded), filled with seeded values
+    g = torch.Generator().manual_seed(0)
+    sd = collections.OrderedDict((k, torch.randn(shape, generator=g))
+                                 for k, shape in RR.value('state_dict_layout/r50_fpn_rpn_checkpoint', compute).items())
     sd['bbox_head.fc_cls.weight'] = torch.zeros(1231, 1024)      # plain Faster R-CNN classifier
     sd['bbox_head.fc_cls.bias'] = torch.zeros(1231)
     path = str(tmp_path / 'faster_rcnn_r50_fpn_1x_lvis.pth')
     torch.save(dict(meta=dict(mmdet_version='1.0.rc0'), state_dict=sd), path)
-    cfg = bgs.Config.fromfile(os.path.join(ref_import.REFERENCE_ROOT,
-                                           'configs/bags/gs_faster_rcnn_r50_fpn_1x_lvis_with0_bg8.py'))
+    cfg = RR.config('configs/bags/gs_faster_rcnn_r50_fpn_1x_lvis_with0_bg8.py')
     paths = gs_tables.save_group_tables(str(tmp_path), *gs_tables.synthetic_group_tables())
     gs = cfg.model.bbox_head.gs_config
     gs.label2binlabel, gs.pred_slice, gs.fg_split = (paths['label2binlabel'], paths['pred_slice'],
@@ -192,26 +197,30 @@ def test_build_optimizer_plain_and_paramwise_rules():
 
 
 def test_build_optimizer_paramwise_equals_the_executed_reference():
-    from oracle import ref_import
-    if not ref_import.reference_available():
-        pytest.skip('reference tree not present')
-    ref_import.install_stubs()
-    try:
-        from mmdet.apis.train import build_optimizer as ref_build
-    except Exception as e:                                                # the apis module pulls mmcv.runner etc.
-        pytest.skip('reference apis.train not importable under the stubs: %r' % (e,))
     from balancedgroupsoftmax_amd import train
     from balancedgroupsoftmax_amd.config import to_config_dict
     m = _tiny_model()
-    for pw in (None, dict(bias_lr_mult=2., bias_decay_mult=0., norm_decay_mult=0.5), dict(bias_lr_mult=3.)):
+    index = {id(p): i for i, p in enumerate(m.parameters())}
+    keys = ('lr', 'momentum', 'weight_decay', 'dampening', 'nesterov')
+
+    def groups(opt):    # each group: the indices of its parameters in m.parameters() and its settings
+        return [dict(params=[index[id(p)] for p in g['params']], **{k: g[k] for k in keys}) for g in opt.param_groups]
+    for j, pw in enumerate((None, dict(bias_lr_mult=2., bias_decay_mult=0., norm_decay_mult=0.5),
+                            dict(bias_lr_mult=3.))):
         cfg = dict(type='SGD', lr=0.02, momentum=0.9, weight_decay=1e-4)
         if pw is not None:
             cfg['paramwise_options'] = pw
-        mine, ref = train.build_optimizer(m, cfg), ref_build(m, to_config_dict(cfg))
-        assert len(mine.param_groups) == len(ref.param_groups)
-        for a, b in zip(mine.param_groups, ref.param_groups):
-            assert [id(p) for p in a['params']] == [id(p) for p in b['params']]
-            for k in ('lr', 'momentum', 'weight_decay', 'dampening', 'nesterov'):
+
+        def compute():
+            ref_import.install_stubs()
+            from mmdet.apis.train import build_optimizer as ref_build
+            return groups(ref_build(m, to_config_dict(cfg)))
+        ref = RR.value('build_optimizer/case%d' % j, compute)
+        mine = groups(train.build_optimizer(m, cfg))
+        assert len(mine) == len(ref)
+        for a, b in zip(mine, ref):
+            assert a['params'] == b['params']
+            for k in keys:
                 assert a[k] == b[k], k
 
 
@@ -298,9 +307,11 @@ def test_fp16_decorators_incl_out_fp16_and_out_fp32():
         auto_fp16()(lambda self, x: x)(object(), f32)
 
 
-@pytest.mark.skipif(not ref_import.reference_available(), reason='reference tree not present')
 def test_fp16_decorators_equal_the_executed_reference_decorators():
-    ref_import.install_stubs()
-    from mmdet.core.fp16.decorators import auto_fp16 as ref_auto, force_fp32 as ref_force
     from balancedgroupsoftmax_amd.fp16_utils import auto_fp16, force_fp32
-    assert _fp16_calls(_decorated_module(auto_fp16, force_fp32)) == _fp16_calls(_decorated_module(ref_auto, ref_force))
+
+    def compute():
+        ref_import.install_stubs()
+        from mmdet.core.fp16.decorators import auto_fp16 as ref_auto, force_fp32 as ref_force
+        return _fp16_calls(_decorated_module(ref_auto, ref_force))
+    assert _fp16_calls(_decorated_module(auto_fp16, force_fp32)) == RR.value('fp16_decorators/calls', compute)

@@ -10,9 +10,9 @@ import torch
 import balancedgroupsoftmax_amd as bgs
 from balancedgroupsoftmax_amd import gs_tables, train
 from oracle import mask_oracle, ref_import, tensor_forms
+from tests import reference_record as RR
 from tests.golden import make_golden_htc as G
 
-needs_ref = pytest.mark.skipif(not ref_import.reference_available(), reason='reference tree absent')
 GOLD = os.path.join(os.path.dirname(G.__file__), 'htc_heads_golden.npz')
 
 
@@ -63,20 +63,20 @@ def test_htc_mask_head_torch_path_vs_executed_reference_golden():
         assert abs(got - float(z['msk/loss'][0])) < 2e-6
 
 
-@needs_ref
 def test_htc_heads_state_dict_matches_reference_modules():
-    ref_import.install_stubs()
-    from mmdet.models.mask_heads.fused_semantic_head import FusedSemanticHead as RefSem
-    from mmdet.models.mask_heads.htc_mask_head import HTCMaskHead as RefMask
-    for ref, mine in ((RefSem(**G.semantic_head_cfg()), _semantic_head()),
-                      (RefMask(**G.mask_head_cfg()), _mask_head())):
-        a = {k: tuple(v.shape) for k, v in ref.state_dict().items()}
-        b = {k: tuple(v.shape) for k, v in mine.state_dict().items()}
-        assert a == b
+    def compute():
+        ref_import.install_stubs()
+        from mmdet.models.mask_heads.fused_semantic_head import FusedSemanticHead as RefSem
+        from mmdet.models.mask_heads.htc_mask_head import HTCMaskHead as RefMask
+        return dict(semantic=RR.signature(RefSem(**G.semantic_head_cfg())),
+                    mask=RR.signature(RefMask(**G.mask_head_cfg())))
+    ref = RR.value('state_dict_layout/htc_heads', compute)
+    assert RR.signature(_semantic_head()) == ref['semantic']
+    assert RR.signature(_mask_head()) == ref['mask']
 
 
 def _load_htc_cfg(tmp_path, name='gs_htc_x101_64x4d_fpn_20e_16gpu_lvis.py', depth=None):
-    cfg = bgs.Config.fromfile(os.path.join(ref_import.REFERENCE_ROOT, 'configs/bags', name))
+    cfg = RR.config('configs/bags/' + name)
     paths = gs_tables.save_group_tables(str(tmp_path), *gs_tables.synthetic_group_tables())
     for h in cfg.model.bbox_head:
         h.gs_config.label2binlabel, h.gs_config.pred_slice, h.gs_config.fg_split = (
@@ -87,7 +87,6 @@ def _load_htc_cfg(tmp_path, name='gs_htc_x101_64x4d_fpn_20e_16gpu_lvis.py', dept
     return cfg
 
 
-@needs_ref
 def test_htc_builds_from_reference_config_with_the_reference_detectors_state_dict(tmp_path):
     """configs/bags/gs_htc_x101_64x4d_fpn_20e_16gpu_lvis.py builds unmodified (tables redirected)
     and its parameter names / shapes equal those of the reference's own ``HybridTaskCascade`` built
@@ -103,17 +102,17 @@ def test_htc_builds_from_reference_config_with_the_reference_detectors_state_dic
     assert cfg.selectp == 3
     params = train.select_training_param(mine, cfg.selectp)
     assert len(params) == 6 and sum(p.numel() for p in params) == 3 * (1236 * 1024 + 1236)
-    ref_import.install_stubs()
-    from mmdet.models import build_detector as ref_build
-    cfg2 = _load_htc_cfg(tmp_path, depth=50)
-    ref = ref_build(cfg2.model, train_cfg=cfg2.train_cfg, test_cfg=cfg2.test_cfg)
-    a = {k: tuple(v.shape) for k, v in ref.state_dict().items()}
-    b = {k: tuple(v.shape) for k, v in mine.state_dict().items()}
-    assert a == b and len(a) > 400
-    mine.load_state_dict(ref.state_dict())          # a reference checkpoint drops in
+    def compute():
+        ref_import.install_stubs()
+        from mmdet.models import build_detector as ref_build
+        cfg2 = _load_htc_cfg(tmp_path, depth=50)
+        return RR.signature(ref_build(cfg2.model, train_cfg=cfg2.train_cfg, test_cfg=cfg2.test_cfg))
+    a = RR.value('state_dict_layout/htc_r50_detector', compute)
+    assert RR.signature(mine) == a and len(a) > 400
+    # a reference checkpoint (its keys and shapes) drops in
+    mine.load_state_dict({k: torch.zeros(shape) for k, shape in a.items()})
 
 
-@needs_ref
 def test_htc_dconv_config_is_refused_loudly(tmp_path):
     """The second HTC config adds deformable convolutions (dcn c3-c5) and multi-scale training:
     deformable conv has no kernel here, and the constructor says so instead of building a model

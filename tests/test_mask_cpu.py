@@ -9,6 +9,7 @@ import torch
 
 import balancedgroupsoftmax_amd as bgs
 from oracle import mask_oracle, ref_import
+from tests import reference_record as RR
 from tests.golden import make_golden_mask
 
 GOLD = os.path.join(os.path.dirname(make_golden_mask.__file__), 'mask_head_golden.npz')
@@ -60,39 +61,45 @@ def test_mask_target_single_crops_like_numpy_slicing():
 
 
 def test_fcn_mask_head_state_dict_matches_reference_module():
-    if not ref_import.reference_available():
-        pytest.skip('reference tree absent')
-    ref_import.install_stubs()
-    from mmdet.models.mask_heads.fcn_mask_head import FCNMaskHead as RefHead
-    ref = RefHead(num_convs=4, in_channels=256, conv_out_channels=256, num_classes=1231)
     mine = bgs.build_head(dict(type='FCNMaskHead', num_convs=4, in_channels=256,
                                conv_out_channels=256, num_classes=1231,
                                loss_mask=dict(type='CrossEntropyLoss', use_mask=True,
                                               loss_weight=1.0)))
-    a = {k: tuple(v.shape) for k, v in ref.state_dict().items()}
-    b = {k: tuple(v.shape) for k, v in mine.state_dict().items()}
-    assert a == b
+    x = torch.randn(2, 256, 14, 14, generator=torch.Generator().manual_seed(0))
+    lab = torch.tensor([3, 1200])
+    # recorded: a seeded sample of the output channels (the whole output is ~8 MB); the whole output is compared
+    # where the reference is present
+    sel = torch.tensor(sorted(set(range(0, 1231, 41)) | {3, 1200}))
+    live = {}
+
+    def compute():
+        ref_import.install_stubs()
+        from mmdet.models.mask_heads.fcn_mask_head import FCNMaskHead as RefHead
+        ref = RefHead(num_convs=4, in_channels=256, conv_out_channels=256, num_classes=1231)
+        with torch.no_grad():
+            mask_oracle.fill_mask_head(ref.state_dict(), 7)
+            live['out'] = ref(x)
+        return dict(signature=np.array(json.dumps(RR.signature(ref))), out_sample=live['out'][:, sel])
+    rec = RR.arrays('fcn_mask_head/c4_256_1231', compute)
+    assert json.loads(str(rec['signature'])) == RR.signature(mine)
     # the torch restatement over this module's parameter containers (oracle/tensor_forms.py) equals
     # the reference with the same parameters; the module itself refuses CPU tensors
     from oracle import tensor_forms
     with torch.no_grad():
-        mask_oracle.fill_mask_head(ref.state_dict(), 7)
-        mine.load_state_dict(ref.state_dict())
-        x = torch.randn(2, 256, 14, 14)
-        assert torch.allclose(tensor_forms.fcn_mask_forward(mine, x), ref(x), atol=1e-5)
-        lab = torch.tensor([3, 1200])
-        assert torch.allclose(tensor_forms.fcn_mask_forward(mine, x, labels=lab),
-                              ref(x)[torch.arange(2), lab], atol=1e-5)
+        mask_oracle.fill_mask_head(mine.state_dict(), 7)
+        got = tensor_forms.fcn_mask_forward(mine, x)
+        assert torch.allclose(got[:, sel], torch.from_numpy(rec['out_sample']), atol=1e-5)
+        if 'out' in live:
+            assert torch.allclose(got, live['out'], atol=1e-5)
+        exp_lab = torch.from_numpy(rec['out_sample'])[torch.arange(2), [int((sel == c).nonzero()) for c in lab]]
+        assert torch.allclose(tensor_forms.fcn_mask_forward(mine, x, labels=lab), exp_lab, atol=1e-5)
         with pytest.raises(RuntimeError, match='no CPU fallback'):
             mine(x)
 
 
 def test_mask_rcnn_builds_from_reference_config(tmp_path):
-    if not ref_import.reference_available():
-        pytest.skip('reference tree absent')
     from balancedgroupsoftmax_amd import gs_tables
-    cfg = bgs.Config.fromfile(os.path.join(ref_import.REFERENCE_ROOT,
-                                           'configs/bags/gs_mask_rcnn_r50_fpn_1x_lvis.py'))
+    cfg = RR.config('configs/bags/gs_mask_rcnn_r50_fpn_1x_lvis.py')
     counts = gs_tables.synthetic_instance_counts(1231, seed=0)
     paths = gs_tables.save_group_tables(str(tmp_path), *gs_tables.build_group_tables(counts))
     gs = cfg.model.bbox_head.gs_config
@@ -127,14 +134,9 @@ def test_seg_masks_dense_equals_the_executed_reference_get_seg_masks():
     ``FCNMaskHead.get_seg_masks`` (fcn_mask_head.py:125-181) with ``mmcv.imresize`` := the oracle's float32 resize
     and ``mask_util.encode`` := identity: box truncation, w / h, the class channel, threshold, placement and the
     per-class bucketing are the reference's own code; only the cv2 resize is the restatement."""
-    if not ref_import.reference_available():
-        pytest.skip('reference tree absent')
-    ref_import.install_stubs()
-    import mmdet.models.mask_heads.fcn_mask_head as ref_mod
     from balancedgroupsoftmax_amd.config import to_config_dict
     rs = np.random.RandomState(11)
     n, C, S = 7, 6, 28
-    ref = ref_mod.FCNMaskHead(num_convs=1, in_channels=8, conv_out_channels=8, num_classes=C)
     logits = torch.from_numpy((rs.standard_normal((n, C, S, S)) * 2).astype(np.float32))
     ori_shape, scale = (97, 131, 3), 1.37
     boxes = np.zeros((n, 5), np.float32)
@@ -145,30 +147,41 @@ def test_seg_masks_dense_equals_the_executed_reference_get_seg_masks():
     boxes[1, :4] = [50.2, 40.7, 50.9, 41.1]                        # a 1 x 1 box
     labels = torch.from_numpy(rs.randint(0, C - 1, n).astype(np.int64))
     cfg = to_config_dict(dict(mask_thr_binary=0.5))
-    saved = (ref_mod.mmcv.imresize, ref_mod.mask_util.encode)
-    ref_mod.mmcv.imresize = lambda img, size: mask_oracle.resize_linear_f32(img, size)
-    ref_mod.mask_util.encode = lambda arr: [np.array(arr[:, :, 0])]
-    try:
-        for rescale in (True, False):
-            # (rescale: boxes live in the network's scale and the masks go to ori_shape; else both in the network's)
-            bx = boxes.copy()
-            if not rescale:
-                bx[:, :4] = np.minimum(bx[:, :4], [[round(131 * scale) - 1, round(97 * scale) - 1] * 2])
-            else:
-                bx[:, :4] = np.minimum(bx[:, :4], [[131 * scale - 0.01, 97 * scale - 0.01] * 2])
-            segms = ref.get_seg_masks(logits, torch.from_numpy(bx), labels, cfg, ori_shape, scale, rescale)
-            probs = torch.sigmoid(logits)[torch.arange(n), labels + 1].numpy()
-            if rescale:
-                ih, iw, sf = 97, 131, scale
-            else:
-                ih, iw, sf = int(np.round(97 * scale)), int(np.round(131 * scale)), 1.0
-            dense = mask_oracle.seg_masks_dense(probs, bx, sf, 0.5, ih, iw)
-            seen = [0] * (C - 1)
+    for rescale in (True, False):
+        # (rescale: boxes live in the network's scale and the masks go to ori_shape; else both in the network's)
+        bx = boxes.copy()
+        if not rescale:
+            bx[:, :4] = np.minimum(bx[:, :4], [[round(131 * scale) - 1, round(97 * scale) - 1] * 2])
+        else:
+            bx[:, :4] = np.minimum(bx[:, :4], [[131 * scale - 0.01, 97 * scale - 0.01] * 2])
+
+        def compute():
+            ref_import.install_stubs()
+            import mmdet.models.mask_heads.fcn_mask_head as ref_mod
+            ref = ref_mod.FCNMaskHead(num_convs=1, in_channels=8, conv_out_channels=8, num_classes=C)
+            saved = (ref_mod.mmcv.imresize, ref_mod.mask_util.encode)
+            ref_mod.mmcv.imresize = lambda img, size: mask_oracle.resize_linear_f32(img, size)
+            ref_mod.mask_util.encode = lambda arr: [np.array(arr[:, :, 0])]
+            try:
+                segms = ref.get_seg_masks(logits, torch.from_numpy(bx), labels, cfg, ori_shape, scale, rescale)
+            finally:
+                ref_mod.mmcv.imresize, ref_mod.mask_util.encode = saved
+            # the masks in the order of the detections, and how many each class bucket holds
+            seen, out = [0] * (C - 1), {'per_class': np.array([len(b) for b in segms], np.int64)}
             for i in range(n):
                 lab = int(labels[i])
-                m = segms[lab][seen[lab]]
+                out['det%d' % i] = segms[lab][seen[lab]]
                 seen[lab] += 1
-                assert m.shape == (ih, iw) and np.array_equal(m, dense[i]), (rescale, i)
-            assert dense.sum() > 0
-    finally:
-        ref_mod.mmcv.imresize, ref_mod.mask_util.encode = saved
+            return out
+        rec = RR.arrays('seg_masks/rescale%d' % rescale, compute)
+        assert rec['per_class'].tolist() == np.bincount(labels.numpy(), minlength=C - 1).tolist()
+        probs = torch.sigmoid(logits)[torch.arange(n), labels + 1].numpy()
+        if rescale:
+            ih, iw, sf = 97, 131, scale
+        else:
+            ih, iw, sf = int(np.round(97 * scale)), int(np.round(131 * scale)), 1.0
+        dense = mask_oracle.seg_masks_dense(probs, bx, sf, 0.5, ih, iw)
+        for i in range(n):
+            m = rec['det%d' % i]
+            assert m.shape == (ih, iw) and np.array_equal(m, dense[i]), (rescale, i)
+        assert dense.sum() > 0

@@ -81,7 +81,7 @@ class StandInStep(object):
         return step
 
 
-def _worker(rank, world, port, out_path):
+def _worker(rank, world, port, out_path, full=True):
     os.environ['MASTER_ADDR'] = '127.0.0.1'
     os.environ['MASTER_PORT'] = str(port)
     torch.set_num_threads(1)
@@ -89,7 +89,7 @@ def _worker(rank, world, port, out_path):
     dist.init_process_group('gloo', rank=rank, world_size=world, timeout=datetime.timedelta(seconds=60))
     import bench_dist
     step = StandInStep(rank, world)
-    args = types.SimpleNamespace(steps=5, warmup=2, imgs=2)
+    args = types.SimpleNamespace(steps=5, warmup=2, imgs=2, full=full)     # (full: bench.py --full, the diagnostics)
 
     def emit(f):
         f = {k: v for k, v in f.items() if k != 'step_fn'}
@@ -100,7 +100,7 @@ def _worker(rank, world, port, out_path):
     dist.destroy_process_group()
 
 
-def run_scenario(env, world=8, port=None):
+def run_scenario(env, world=8, port=None, full=True):
     """-> (list of emitted lines (dicts), wall seconds, exit codes ok)."""
     port = port or (36000 + (os.getpid() * 7 + int(time.time())) % 2000)
     fd, out_path = tempfile.mkstemp(prefix='bench_dist_dry_', suffix='.jsonl')
@@ -113,7 +113,7 @@ def run_scenario(env, world=8, port=None):
     t0 = time.time()
     ok = True
     try:
-        mp.spawn(_worker, args=(world, port, out_path), nprocs=world, join=True)
+        mp.spawn(_worker, args=(world, port, out_path, full), nprocs=world, join=True)
     except Exception as e:      # a rank that left with a non-zero code
         ok = False
         sys.stderr.write('scenario raised: %r\n' % (e,))

@@ -14,7 +14,7 @@ timeout 1200 python -m pytest tests -m gpu -q --timeout 600 > $OUT/pytest_gpu.lo
 tail -6 $OUT/pytest_gpu.log | cut -c1-300
 echo "== smoke"; timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?" | tee -a $OUT/smoke.log; tail -3 $OUT/smoke.log | cut -c1-300
 echo "== bench"
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-600 $OUT/bench.json; tail -3 $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; cut -c1-600 $OUT/bench.json; tail -3 $OUT/bench.err
 echo "== rocprofv3 kernel trace (eager, 8 steps; BGS_LEVEL_FORK=0: with the small pyramid levels on a side stream the"
 echo "   durations of overlapping kernels are not additive, so the per-family table is taken on one stream)"
 (cd /tmp && BGS_LEVEL_FORK=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o det -- python $R/bench.py --workload detector --steps 6 --warmup 2 --no-cpu-baseline --no-extras --no-roofline --no-graph > $OUT/prof_bench.json 2> $OUT/prof.err; echo "rocprof rc=$?")

@@ -24,7 +24,7 @@ smoke)
   timeout 600 python __graft_entry__.py > $OUT/smoke.log 2>&1; echo "smoke rc=$?" | tee -a $OUT/smoke.log; tail -3 $OUT/smoke.log
   ;;
 bench)
-  timeout 1200 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
+  timeout 1200 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
   python - <<PY
 import json
 d=json.loads([l for l in open('$OUT/bench.json') if l.startswith('{')][-1])
@@ -39,7 +39,7 @@ print({k:(v.get('ms_per_step'), v.get('error')) for k,v in (d.get('also_measured
 PY
   ;;
 benchquick)
-  timeout 900 python bench.py --no-extras > $OUT/bench_quick.json 2> $OUT/bench_quick.err; echo "bench rc=$?"; tail -3 $OUT/bench_quick.err
+  timeout 900 python bench.py --full --no-extras > $OUT/bench_quick.json 2> $OUT/bench_quick.err; echo "bench rc=$?"; tail -3 $OUT/bench_quick.err
   python - <<PY
 import json
 d=json.loads([l for l in open('$OUT/bench_quick.json') if l.startswith('{')][-1])
@@ -54,7 +54,7 @@ PY
   ;;
 dist)
   # the N > 1 code path on the one GPU: two ranks over gloo (diagnostics, dist-graph children + fallback)
-  BGS_BENCH_ONE_DEVICE=1 BGS_DIST_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --no-roofline > $OUT/dist2.json 2> $OUT/dist2.err; echo "dist2 rc=$?"; tail -4 $OUT/dist2.err
+  BGS_BENCH_ONE_DEVICE=1 BGS_DIST_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 5 --warmup 2 --no-roofline > $OUT/dist2.json 2> $OUT/dist2.err; echo "dist2 rc=$?"; tail -4 $OUT/dist2.err
   python - <<PY
 import json
 ls=[l for l in open('$OUT/dist2.json') if l.startswith('{')]
@@ -76,7 +76,7 @@ profsp0)
   find $OUT/prof0 -name "*kernel_trace.csv" -size +30M -delete
   ;;
 gsprof)
-  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/gsprof -o gs -- python $R/bench.py --workload gs_head --steps 50 --warmup 5 --no-graph --no-cpu-baseline > $OUT/gsprof_bench.json 2> $OUT/gsprof.err; echo "rocprof rc=$?")
+  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/gsprof -o gs -- python $R/bench.py --full --workload gs_head --steps 50 --warmup 5 --no-graph --no-cpu-baseline > $OUT/gsprof_bench.json 2> $OUT/gsprof.err; echo "rocprof rc=$?")
   for f in $(find $OUT/gsprof -name "*kernel_stats.csv"); do cut -c1-150 $f | head -14; done
   ;;
 gstests)
@@ -89,7 +89,7 @@ gsab)
 gspmc)
   # HBM traffic of the head kernel: FETCH_SIZE / WRITE_SIZE in separate rocprofv3 --pmc passes (kernel-trace only)
   for C in FETCH_SIZE WRITE_SIZE; do
-    (cd /tmp && timeout -k 3 150 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/gspmc/$C -o p -- python $R/bench.py --workload gs_head --steps 20 --warmup 2 --no-graph --no-cpu-baseline > $OUT/gspmc_$C.log 2> $OUT/gspmc_$C.err; echo "pmc $C rc=$?")
+    (cd /tmp && timeout -k 3 150 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/gspmc/$C -o p -- python $R/bench.py --full --workload gs_head --steps 20 --warmup 2 --no-graph --no-cpu-baseline > $OUT/gspmc_$C.log 2> $OUT/gspmc_$C.err; echo "pmc $C rc=$?")
   done
   python - <<PY
 import csv, glob, collections

@@ -31,8 +31,8 @@ group halo python $R/tools/conv_p2_once.py
 BGS_CONV1X1_BRES=0 group lat0_ring python $R/tools/conv_layer_once.py 2 200 336 256 256 1 1
 BGS_CONV1X1_BRES=2 group lat0_bres python $R/tools/conv_layer_once.py 2 200 336 256 256 1 1
 mkdir -p $OUT/gs
-pass gs fetch "FETCH_SIZE" python $R/bench.py --workload gs_head --steps 20 --warmup 2 --no-graph --no-cpu-baseline
-pass gs write "WRITE_SIZE" python $R/bench.py --workload gs_head --steps 20 --warmup 2 --no-graph --no-cpu-baseline
+pass gs fetch "FETCH_SIZE" python $R/bench.py --full --workload gs_head --steps 20 --warmup 2 --no-graph --no-cpu-baseline
+pass gs write "WRITE_SIZE" python $R/bench.py --full --workload gs_head --steps 20 --warmup 2 --no-graph --no-cpu-baseline
 python - <<PY
 import csv, glob, collections, os
 keys = {'halo': ('halo_bfx4',), 'lat0_ring': ('conv_igemm_bfx_dma',), 'lat0_bres': ('conv1x1_bres',), 'gs': ('gs_head_fused', 'gs_loss_rowwave')}

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/$C -o gs -- python $R/bench.py --workload gs_head --steps 20 --warmup 2 --no-graph --no-cpu-baseline > $OUT/$C.json 2> $OUT/$C.err
+  timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/$C -o gs -- python $R/bench.py --full --workload gs_head --steps 20 --warmup 2 --no-graph --no-cpu-baseline > $OUT/$C.json 2> $OUT/$C.err
   echo "$C rc=$?"
   ls $OUT/$C
 done
