@@ -1,17 +1,20 @@
-"""Signature-compatible stand-ins for the two pybind11 extension modules the reference imports
-on this path, backed by ``libbgs.so``:
+"""Signature-compatible stand-ins for the extension modules the reference imports on this path,
+backed by ``libbgs.so``:
 
 * :mod:`.roi_align_cuda` — ``mmdet/ops/roi_align/src/roi_align_cuda.cpp:27-85``
   (``forward`` / ``backward``; imported by ``mmdet/ops/roi_align/roi_align.py:6``);
 * :mod:`.nms_cuda`       — ``mmdet/ops/nms/src/nms_cuda.cpp:8-17`` (``nms``; imported by
-  ``mmdet/ops/nms/nms_wrapper.py:4``).
+  ``mmdet/ops/nms/nms_wrapper.py:4``);
+* :mod:`.soft_nms_cpu`   — ``mmdet/ops/nms/src/soft_nms_cpu.pyx:22-127`` (``soft_nms_cpu``; imported by
+  ``mmdet/ops/nms/nms_wrapper.py:5``).  It runs on the current GPU despite its name.
 
 A maintainer of the reference drops them in without touching any caller::
 
     import sys
-    from balancedgroupsoftmax_amd.compat import roi_align_cuda, nms_cuda
+    from balancedgroupsoftmax_amd.compat import roi_align_cuda, nms_cuda, soft_nms_cpu
     sys.modules['mmdet.ops.roi_align.roi_align_cuda'] = roi_align_cuda
     sys.modules['mmdet.ops.nms.nms_cuda'] = nms_cuda
+    sys.modules['mmdet.ops.nms.soft_nms_cpu'] = soft_nms_cpu
 
 Same argument order, layouts (NCHW features / outputs, unsorted ``dets``), ownership (the caller
 allocates ``output`` / ``bottom_grad``), return values (``1`` / ``0`` + "wrong roi size",
@@ -19,4 +22,4 @@ original-order keep indices) and input checks (CUDA + contiguous) as the extensi
 ABI underneath is NHWC / pre-sorted (``include/bgs.h``); the transposes and the score sort are done
 here, on the device.
 """
-from . import nms_cuda, roi_align_cuda  # noqa: F401
+from . import nms_cuda, roi_align_cuda, soft_nms_cpu  # noqa: F401

@@ -1766,6 +1766,33 @@ def nms_batched(boxes, counts, iou_thr, iou_mode=0, max_keep=0):
     return keep, keep_count
 
 
+SOFT_NMS_METHODS = {'hard': 0, 'linear': 1, 'gaussian': 2}
+
+
+def soft_nms_batched(dets, counts, iou_thr, method='linear', sigma=0.5, min_score=1e-3):
+    """dets ``[P,nmax,5]`` in candidate order per problem, counts ``[P]`` i32 -> ``order [P,nmax]`` i32 (candidate
+    indices in selection order), ``scores [P,nmax]`` f32 (decayed score at selection), ``keep_count [P]`` i32
+    (``bgs_soft_nms_batched``: one launch, no host sync).  ``method``: ``'linear'`` / ``'gaussian'`` / ``'hard'``
+    or its code 1 / 2 / 0."""
+    _require_cuda(dets, counts)
+    code = SOFT_NMS_METHODS.get(method, method)
+    if code not in (0, 1, 2):
+        raise ValueError('Invalid method for SoftNMS: {}'.format(method))
+    lib = capi.load()
+    dets = _f32c(dets)
+    assert dets.dim() == 3 and dets.shape[2] == 5 and counts.dtype == torch.int32
+    P, nmax, _ = dets.shape
+    dev = dets.device
+    order = torch.empty((P, nmax), dtype=torch.int32, device=dev)
+    scores = torch.empty((P, nmax), dtype=torch.float32, device=dev)
+    keep_count = torch.empty((P,), dtype=torch.int32, device=dev)
+    rc = lib.bgs_soft_nms_batched(capi.ptr(dets), capi.ptr(counts.contiguous()), P, nmax, float(iou_thr), int(code),
+                                  float(sigma), float(min_score), capi.ptr(order), capi.ptr(scores),
+                                  capi.ptr(keep_count), capi.current_stream(dev))
+    capi.check('bgs_soft_nms_batched', rc)
+    return order, scores, keep_count
+
+
 def nms_gather(boxes, keep, keep_count):
     """``boxes [R,nmax,5]``, ``keep [R,nmax]`` / ``keep_count [R]`` of :func:`nms_batched` ->
     ``(kept [R,nmax,5], scores [R,nmax])``: the kept boxes in fixed-shape rows, score -1 in the slots

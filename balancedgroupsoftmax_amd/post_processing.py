@@ -15,6 +15,10 @@ the classes are the batch dimension of the NMS kernel pair in ``csrc/nms.hip``:
 
 The only host synchronisation is the final size of the result (the output is dynamic-shaped
 by contract).
+
+``nms_cfg=dict(type='soft_nms', iou_thr, method='linear'|'gaussian', sigma=0.5, min_score=1e-3)`` (the
+configs' commented test setting) runs the reference's per-class ``soft_nms_cpu`` for all classes in ONE
+``bgs_soft_nms_batched`` launch (``csrc/soft_nms.hip``), bit-identical to it; see ``_multiclass_soft_nms``.
 """
 import numpy as np
 import torch
@@ -29,8 +33,10 @@ def multiclass_nms(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1, s
     reference: class-major (original row order inside a class) when nothing is cut, by descending score when ``max_num`` cuts."""
     cfg = dict(nms_cfg)
     nms_type = cfg.pop('type', 'nms')
+    if nms_type == 'soft_nms':
+        return _multiclass_soft_nms(multi_bboxes, multi_scores, score_thr, cfg, max_num, score_factors)
     if nms_type != 'nms':
-        raise NotImplementedError('only type="nms" is used by the BAGS configs (got %r)' % nms_type)
+        raise NotImplementedError('only type="nms" and type="soft_nms" are supported (got %r)' % nms_type)
     iou_thr = float(cfg.pop('iou_thr'))
     n, C = multi_scores.shape
     dev = multi_scores.device
@@ -69,6 +75,59 @@ def multiclass_nms(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1, s
     flat_scores = torch.where(slot_ok, kept[..., 4], kept.new_full((), -float('inf'))).reshape(-1)
     _, top = flat_scores.topk(max_num)
     return kept.view(-1, 5)[top], labels_all.reshape(-1)[top]
+
+
+def _multiclass_soft_nms(multi_bboxes, multi_scores, score_thr, cfg, max_num, score_factors):
+    """``type='soft_nms'``: the reference's per-class ``nms_wrapper.soft_nms`` (nms_wrapper.py:50-76 ->
+    soft_nms_cpu.pyx) for all classes in ONE ``bgs_soft_nms_batched`` launch.  Per class the candidates are the
+    rows with raw score ``> score_thr`` in ORIGINAL row order (the .pyx's in-place permutation, and so its tie
+    order, depends on it); survivors come out class-major in selection order with their decayed scores; more than
+    ``max_num`` -> the ``max_num`` best by decayed score, descending (ties in concatenation order)."""
+    method = cfg.pop('method', 'linear')
+    if method not in ('linear', 'gaussian'):                 # nms_wrapper.py:65-67, before any device work
+        raise ValueError('Invalid method for SoftNMS: {}'.format(method))
+    iou_thr = float(cfg.pop('iou_thr'))
+    sigma = float(cfg.pop('sigma', 0.5))
+    min_score = float(cfg.pop('min_score', 1e-3))
+    n, C = multi_scores.shape
+    dev = multi_scores.device
+    P = C - 1
+    if n == 0 or P <= 0:
+        return multi_bboxes.new_zeros((0, 5)), multi_bboxes.new_zeros((0,), dtype=torch.long)
+    scores = multi_scores[:, 1:].t().float()                        # [P, n]
+    live = multi_scores[:, 1:].t() > score_thr                      # the threshold is on the raw score
+    if score_factors is not None:
+        scores = scores * score_factors.view(1, n).float()
+    counts = live.sum(dim=1).to(torch.int32)
+    # live rows first, each class's in original row order
+    idx = torch.sort((~live).to(torch.uint8), dim=1, stable=True)[1]   # [P, n]
+    if multi_bboxes.shape[1] == 4:
+        boxes = multi_bboxes.float()[idx]                            # [P, n, 4]
+    else:
+        per_cls = multi_bboxes.float().view(n, C, 4)[:, 1:].permute(1, 0, 2)   # [P, n, 4] view
+        boxes = torch.gather(per_cls, 1, idx[..., None].expand(-1, -1, 4))
+    dets = torch.cat([boxes, torch.gather(scores, 1, idx)[..., None]], dim=2).contiguous()
+    order, sel_scores, keep_n = BF.soft_nms_batched(dets, counts, iou_thr, method, sigma, min_score)
+    rows = torch.cat([torch.gather(boxes, 1, order.long().clamp(min=0, max=n - 1)[..., None].expand(-1, -1, 4)),
+                      sel_scores[..., None]], dim=2)                 # [P, n, 5] in selection order
+    slot = torch.arange(n, device=dev).view(1, n)
+    slot_ok = slot < keep_n.view(P, 1)
+    total = int(keep_n.sum())                       # the one sync: the result is dynamic-shaped
+    if total == 0:
+        return multi_bboxes.new_zeros((0, 5)), multi_bboxes.new_zeros((0,), dtype=torch.long)
+    labels_all = torch.arange(P, device=dev).view(P, 1).expand(P, n)
+    if max_num < 0 or total <= max_num:
+        # class-major, selection order inside a class: row (p, j) goes to offs[p] + j, padding to a spare row
+        offs = torch.cumsum(keep_n.long(), 0) - keep_n.long()
+        dest = torch.where(slot_ok, offs.view(P, 1) + slot, torch.full_like(slot, total)).reshape(-1)
+        out_b = rows.new_empty((total + 1, 5))
+        out_l = labels_all.new_empty((total + 1,))
+        out_b[dest] = rows.reshape(-1, 5)
+        out_l[dest] = labels_all.reshape(-1)
+        return out_b[:total], out_l[:total]
+    flat_scores = torch.where(slot_ok, sel_scores, sel_scores.new_full((), -float('inf'))).reshape(-1)
+    top = torch.sort(flat_scores, descending=True, stable=True)[1][:max_num]
+    return rows.reshape(-1, 5)[top], labels_all.reshape(-1)[top]
 
 
 def bbox2result(bboxes, labels, num_classes):

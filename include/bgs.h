@@ -566,6 +566,20 @@ int bgs_gather_boxes(const float* flat, const long long* idx, const float* score
 int bgs_nms_merge_select(const float* boxes, const int* keep, const int* keep_count, int N, int L, int nmax,
                          int num, float* props, unsigned char* valid, bgs_stream_t stream);
 
+/* Batched soft-NMS, entirely on the device, ONE launch for P problems (the classes of multiclass_nms).
+ *   Replaces nms_wrapper.soft_nms -> soft_nms_cpu (mmdet/ops/nms/nms_wrapper.py:50-76,
+ *   src/soft_nms_cpu.pyx:22-127: the selection scan :46-71, the decay :76-109 and the swap-with-last
+ *   discard :111-120), bit-identical including its in-place permutation (ties go to the lowest position).
+ *   dets [P, nmax, 5] float (x1,y1,x2,y2,score) in CANDIDATE order (not sorted); counts [P] int32;
+ *   method 0 hard (`ov > iou_thr` -> weight 0), 1 linear, 2 gaussian (exp in double, as np.exp);
+ *   legacy +1 IoU, decay only where iw > 0 and ih > 0, discard when the new score < min_score;
+ *   order [P, nmax] int32: candidate indices in selection order, scores [P, nmax]: the score each had when
+ *   selected, first keep_count[p] entries valid.  Caller-owned outputs, no workspace.  nmax <= 4096
+ *   (BGS_ERR_UNSUPPORTED beyond); unknown method: BGS_ERR_INVALID_ARG. */
+int bgs_soft_nms_batched(const float* dets, const int* counts, int P, int nmax, float iou_thr, int method,
+                         float sigma, float min_score, int* order, float* scores, int* keep_count,
+                         bgs_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Target assignment without the [G, A] IoU matrix.  Replaces MaxIoUAssigner.assign /
  *   assign_wrt_overlaps (mmdet/core/bbox/assigners/max_iou_assigner.py:47-180, incl. its CPU

@@ -3,6 +3,8 @@
 batched NMS, max 300 dets) — informational, not the headline metric.
 
     python tools/infer_time.py [iters]
+    python tools/infer_time.py --nms soft_nms [iters]    # simple_test with the configs' commented soft-NMS setting
+                                                         # (iou_thr 0.5, min_score 0.05) next to hard NMS
 """
 import os
 import sys
@@ -19,8 +21,57 @@ from balancedgroupsoftmax_amd.config import to_config_dict  # noqa: E402
 from bench import detector_cfg  # noqa: E402
 
 
+SOFT_NMS = dict(type='soft_nms', iou_thr=0.5, min_score=0.05)
+
+
+def _time(fn, iters):
+    for _ in range(3):
+        out = fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e3, out
+
+
+def soft_vs_hard(model, img, metas, iters):
+    """simple_test and the 1230-class multiclass_nms alone, hard NMS and soft-NMS on the same model and image."""
+    from balancedgroupsoftmax_amd.post_processing import multiclass_nms
+    hard_cfg = model.test_cfg
+    soft = dict(hard_cfg)
+    soft['rcnn'] = dict(hard_cfg.rcnn, nms=SOFT_NMS)
+    soft_cfg = to_config_dict(soft)
+    with torch.no_grad():
+        x = model.extract_feat(img)
+        props = model.simple_test_rpn(x, metas, model.test_cfg.rpn)
+        _, _, scores = model.simple_test_bboxes(x, metas, props, model.test_cfg.rcnn)    # the model's own inputs
+        rois = torch.cat([props[0][0].new_zeros((props[0][0].size(0), 1)), props[0][0][:, :4]], 1)
+        cls_score, bbox_pred = model.bbox_head(model.bbox_roi_extractor(x[:4], rois), nhwc=True)
+        boxes, _ = model.bbox_head.get_det_bboxes(rois, cls_score, bbox_pred, metas[0]['img_shape'], 1.0,
+                                                  rescale=True, cfg=None)
+    out = {}
+    for name, cfg, nms in (('hard', hard_cfg, dict(type='nms', iou_thr=0.5)), ('soft_nms', soft_cfg, SOFT_NMS)):
+        model.test_cfg = cfg
+        with torch.no_grad():
+            ms, res = _time(lambda: model(img, metas, return_loss=False, rescale=True), iters)
+            ms_nms, _ = _time(lambda: multiclass_nms(boxes, scores, 0.0, nms, 300), iters)
+        out[name] = dict(simple_test_ms_per_img=round(ms, 3), multiclass_nms_1230x1000_ms=round(ms_nms, 3),
+                         dets=sum(r.shape[0] for r in res))
+    model.test_cfg = hard_cfg
+    import json
+    print(json.dumps(dict(out, soft_nms_cfg=SOFT_NMS, iters=iters)))
+
+
 def main():
-    iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+    argv = sys.argv[1:]
+    nms = 'nms'
+    if '--nms' in argv:
+        k = argv.index('--nms')
+        nms = argv[k + 1]
+        del argv[k:k + 2]
+    assert nms in ('nms', 'soft_nms'), nms
+    iters = int(argv[0]) if argv else 20
     dev = torch.device('cuda:0')
     torch.manual_seed(0)
     model_cfg, train_cfg = detector_cfg(tempfile.mkdtemp(prefix='bgs_tables_'))
@@ -34,6 +85,8 @@ def main():
     img = torch.randn(1, 3, 800, 1344, device=dev)
     metas = [dict(img_shape=(800, 1333, 3), pad_shape=(800, 1344, 3), ori_shape=(800, 1333, 3),
                   scale_factor=1.0, flip=False)]
+    if nms == 'soft_nms':
+        return soft_vs_hard(model, img, metas, iters)
     for _ in range(3):
         res = model(img, metas, return_loss=False, rescale=True)
     torch.cuda.synchronize()
