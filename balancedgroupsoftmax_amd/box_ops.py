@@ -4,6 +4,7 @@ Semantics follow the reference's legacy (+1 width) box convention:
 * ``bbox2delta``  mmdet/core/bbox/transforms.py:6-31
 * ``delta2bbox``  mmdet/core/bbox/transforms.py:34-111 (known-answer doctest :64-77)
 * ``bbox2roi``    mmdet/core/bbox/transforms.py:149-168
+* ``bbox_mapping`` / ``bbox_mapping_back``  mmdet/core/bbox/transforms.py:114-146 (test-time augmentation)
 * ``bbox_target`` mmdet/core/bbox/bbox_target.py:7-61
 """
 import math
@@ -98,3 +99,21 @@ def bbox_target(pos_bboxes_list, neg_bboxes_list, pos_gt_bboxes_list, pos_gt_lab
     if concat:
         cols = [torch.cat(c, 0) for c in cols]
     return tuple(cols)
+
+
+def _geom(img_shape, scale_factor, flip):
+    return (scale_factor, bool(flip), int(img_shape[1]))
+
+
+def bbox_mapping(bboxes, img_shape, scale_factor, flip):
+    """transforms.py:133-138: ``[n, 4k]`` boxes from the original image into a test view (``b * s``, then the flip
+    of ``bbox_flip`` with that view's width ``img_shape[1]``).  One launch (csrc/aug_merge.hip); GPU tensors only."""
+    from . import functional as BF
+    return BF.aug_map_boxes([bboxes], [_geom(img_shape, scale_factor, flip)], back=False)[0]
+
+
+def bbox_mapping_back(bboxes, img_shape, scale_factor, flip):
+    """transforms.py:141-146: ``[n, 4k]`` boxes from a test view back into the original image (the flip first, then
+    ``/ s``).  One launch (csrc/aug_merge.hip); GPU tensors only."""
+    from . import functional as BF
+    return BF.aug_map_boxes([bboxes], [_geom(img_shape, scale_factor, flip)], back=True)[0]

@@ -347,14 +347,121 @@ class TwoStageDetector(nn.Module):
                                             img_meta[0]['ori_shape'], img_meta[0]['scale_factor'], rescale,
                                             encode=encode)
 
+    # ------------------------------------------------------------------ test-time augmentation
+    def extract_feats(self, imgs):
+        """base.py:47-49.  aug_test computes every view's features ONCE and keeps them for the RPN, box and mask
+        passes (the reference recomputes them to save memory; the results are the same)."""
+        assert isinstance(imgs, (list, tuple))
+        return [self.extract_feat(img) for img in imgs]
+
+    def _check_aug(self, img_metas):
+        """The limits of aug_test, raised before any device work."""
+        from . import functional as BF
+        A = len(img_metas)
+        if A > BF.AUG_MAX_VIEWS:
+            raise NotImplementedError('aug_test: at most %d views (got %d)' % (BF.AUG_MAX_VIEWS, A))
+        rpn_cfg = self.test_cfg.get('rpn') if self.test_cfg is not None else None
+        if rpn_cfg is not None and A * int(rpn_cfg.max_num) > 4096:
+            raise NotImplementedError(
+                'aug_test: A x test_cfg.rpn.max_num <= 4096 (the merged proposals go through bgs_nms_batched / '
+                'bgs_topk_sorted_f32, nmax <= 4096); got %d x %d' % (A, int(rpn_cfg.max_num)))
+        for m in img_metas:
+            if not isinstance(m[0]['scale_factor'], float):
+                raise NotImplementedError('aug_test: scale_factor must be a float (keep_ratio=True); the array '
+                                          'form is not built (got %r)' % (m[0]['scale_factor'],))
+
+    @staticmethod
+    def _view_geoms(img_metas):
+        return [(m[0]['scale_factor'], bool(m[0]['flip']), int(m[0]['img_shape'][1])) for m in img_metas]
+
+    def aug_test_rpn(self, feats, img_metas, rpn_test_cfg):
+        """test_mixins.py:14-34 for one image: every view's fixed-shape proposals, merged in the original image
+        scale (``merge_augs.merge_aug_proposals``) -> ``[(props [max_num, 5], valid [max_num])]``."""
+        from .merge_augs import merge_aug_proposals
+        views = [self.simple_test_rpn(x, meta, rpn_test_cfg)[0] for x, meta in zip(feats, img_metas)]
+        return [merge_aug_proposals(views, img_metas, rpn_test_cfg)]
+
+    @staticmethod
+    def _split_proposals(proposal_list):
+        props, valid = proposal_list[0] if isinstance(proposal_list[0], tuple) else (proposal_list[0], None)
+        return props, valid
+
+    def aug_test_bboxes(self, feats, img_metas, proposal_list, rcnn_test_cfg):
+        """test_mixins.py:138-173: the merged proposals mapped into every view (one launch), the box head per view,
+        boxes mapped back and averaged with the scores (one launch), then ``multiclass_nms``."""
+        from . import functional as BF
+        from .merge_augs import merge_aug_bboxes
+        from .post_processing import multiclass_nms
+        props, valid = self._split_proposals(proposal_list)
+        A = len(feats)
+        rois_all = BF.aug_map_boxes([props] * A, self._view_geoms(img_metas), back=False, mode='rois')
+        aug_bboxes, aug_scores = [], []
+        for a, (x, meta) in enumerate(zip(feats, img_metas)):
+            rois = rois_all[a]
+            roi_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
+            cls_score, bbox_pred = self.bbox_head(roi_feats, nhwc=True)
+            bboxes, scores = self.bbox_head.get_det_bboxes(rois, cls_score, bbox_pred, meta[0]['img_shape'],
+                                                           meta[0]['scale_factor'], rescale=False, cfg=None)
+            aug_bboxes.append(bboxes)
+            aug_scores.append(scores)
+        bboxes, scores = merge_aug_bboxes(aug_bboxes, aug_scores, img_metas, rcnn_test_cfg, valid=valid)
+        return multiclass_nms(bboxes, scores, rcnn_test_cfg.score_thr, rcnn_test_cfg.nms, rcnn_test_cfg.max_per_img)
+
+    def aug_test_mask(self, feats, img_metas, det_bboxes, det_labels):
+        """test_mixins.py:207-239 up to ``get_seg_masks``: per detection the merged probability of its own class
+        ``[k, 28, 28]`` (what ``simple_test_mask`` returns); ``det_bboxes`` are in the original image scale."""
+        from . import functional as BF
+        from .merge_augs import merge_aug_masks
+        if det_bboxes.shape[0] == 0:
+            return det_bboxes.new_zeros((0, 28, 28))
+        A = len(feats)
+        rois_all = BF.aug_map_boxes([det_bboxes[:, :4]] * A, self._view_geoms(img_metas), back=False, mode='rois')
+        probs = []
+        for a, x in enumerate(feats):
+            mask_feats = self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], rois_all[a])
+            probs.append(self.mask_head.get_mask_probs(self.mask_head.features(mask_feats, nhwc=True), det_labels))
+        return merge_aug_masks(probs, img_metas, self.test_cfg.rcnn)
+
+    def aug_test(self, imgs, img_metas, rescale=False, proposals=None):
+        """two_stage.py:292-319 for A views of one image.  ``rescale=False``: the boxes are multiplied by the first
+        view's ``scale_factor`` (two_stage.py:305-309).  ``proposals``: merged ``[(props, valid)]`` in the original
+        image scale instead of the RPN (test hook, as in ``simple_test``).  With a mask branch:
+        ``(bbox_results, probs [k, 28, 28])``."""
+        from .post_processing import bbox2result
+        assert self.with_bbox, 'Bbox head must be implemented.'
+        self._check_aug(img_metas)
+        feats = self.extract_feats(imgs)
+        proposal_list = (self.aug_test_rpn(feats, img_metas, self.test_cfg.rpn)
+                         if proposals is None else proposals)
+        det_bboxes, det_labels = self.aug_test_bboxes(feats, img_metas, proposal_list, self.test_cfg.rcnn)
+        if rescale:
+            _det_bboxes = det_bboxes
+        else:
+            _det_bboxes = torch.cat([det_bboxes[:, :4] * img_metas[0][0]['scale_factor'], det_bboxes[:, 4:]], dim=1)
+        bbox_results = bbox2result(_det_bboxes, det_labels, self.bbox_head.num_classes)
+        if not self.with_mask:
+            return bbox_results
+        return bbox_results, self.aug_test_mask(feats, img_metas, det_bboxes, det_labels)
+
     def forward_test(self, imgs, img_metas, **kwargs):
-        """base.py forward_test: one scale only (aug_test / TTA is not on the BAGS path)."""
-        if isinstance(imgs, (list, tuple)):
-            if len(imgs) != 1:
-                raise NotImplementedError('multi-scale aug_test is not part of the BAGS path')
-            imgs, img_metas = imgs[0], img_metas[0]
+        """base.py:78-96.  A list of A views of one image: ``simple_test`` for one view, ``aug_test`` for more.
+        A bare tensor ``imgs`` runs ``simple_test`` directly."""
+        if torch.is_tensor(imgs):
+            with torch.no_grad():
+                return self.simple_test(imgs, img_metas, **kwargs)
+        for var, name in [(imgs, 'imgs'), (img_metas, 'img_metas')]:
+            if not isinstance(var, (list, tuple)):
+                raise TypeError('{} must be a list, but got {}'.format(name, type(var)))
+        num_augs = len(imgs)
+        if num_augs != len(img_metas):
+            raise ValueError('num of augmentations ({}) != num of image meta ({})'.format(len(imgs),
+                                                                                          len(img_metas)))
+        imgs_per_gpu = imgs[0].size(0)
+        assert imgs_per_gpu == 1
         with torch.no_grad():
-            return self.simple_test(imgs, img_metas, **kwargs)
+            if num_augs == 1:
+                return self.simple_test(imgs[0], img_metas[0], **kwargs)
+            return self.aug_test(imgs, img_metas, **kwargs)
 
     def forward(self, img, img_meta, return_loss=True, **kwargs):
         if return_loss:
@@ -505,6 +612,54 @@ class CascadeRCNN(TwoStageDetector):
         cfg = self.test_cfg.rcnn
         det_bboxes, det_labels = multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms,
                                                 cfg.max_per_img)
+        return bbox2result(det_bboxes, det_labels, self.bbox_head[-1].num_classes)
+
+    def _stage_loop(self, x, rois, img_meta, semantic_feat=None):
+        """One view's test-time stage loop (``simple_test``): every stage re-regresses the RoIs with its arg-max
+        class against this view's ``img_meta``; the class logits are averaged over the stages ->
+        ``(bboxes, scores)`` in the view's scale (``get_det_bboxes``, ``rescale=False``)."""
+        ms_scores = []
+        for i in range(self.num_stages):
+            head, ext = self.bbox_head[i], self.bbox_roi_extractor[i]
+            if semantic_feat is None:
+                feats = ext(x[:ext.num_inputs], rois)
+            else:
+                feats = self._fused_roi_feats(ext, x, rois, semantic_feat, 'bbox')
+            cls_score, bbox_pred = head(feats, nhwc=True)
+            ms_scores.append(cls_score)
+            if i < self.num_stages - 1:
+                rois = head.regress_by_class(rois, cls_score.argmax(dim=1), bbox_pred, img_meta[0])
+        cls_score = sum(ms_scores) / float(len(ms_scores))
+        return self.bbox_head[-1].get_det_bboxes(rois, cls_score, bbox_pred, img_meta[0]['img_shape'],
+                                                 img_meta[0]['scale_factor'], rescale=False, cfg=None)
+
+    def _aug_test_dets(self, feats, img_metas, proposals, semantic_feats):
+        """cascade_rcnn.py:445-503 / htc.py:441-504: merged proposals (or the caller's, original scale) mapped into
+        every view, each view's stage loop, boxes and scores merged, ``multiclass_nms``."""
+        from . import functional as BF
+        from .merge_augs import merge_aug_bboxes
+        from .post_processing import multiclass_nms
+        proposal_list = (self.aug_test_rpn(feats, img_metas, self.test_cfg.rpn)
+                         if proposals is None else proposals)
+        props, valid = self._split_proposals(proposal_list)
+        rois_all = BF.aug_map_boxes([props] * len(feats), self._view_geoms(img_metas), back=False, mode='rois')
+        aug_bboxes, aug_scores = [], []
+        for a, (x, meta) in enumerate(zip(feats, img_metas)):
+            bboxes, scores = self._stage_loop(x, rois_all[a], meta, semantic_feats[a])
+            aug_bboxes.append(bboxes)
+            aug_scores.append(scores)
+        bboxes, scores = merge_aug_bboxes(aug_bboxes, aug_scores, img_metas, self.test_cfg.rcnn, valid=valid)
+        cfg = self.test_cfg.rcnn
+        return multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
+
+    def aug_test(self, imgs, img_metas, proposals=None, rescale=False):
+        """cascade_rcnn.py:445-548 (bbox branch): ``rescale`` is ignored, the boxes are in the original image scale
+        (cascade_rcnn.py:507).  ``proposals``: merged ``[(props, valid)]`` in the original scale instead of the
+        RPN."""
+        from .post_processing import bbox2result
+        self._check_aug(img_metas)
+        feats = self.extract_feats(imgs)
+        det_bboxes, det_labels = self._aug_test_dets(feats, img_metas, proposals, [None] * len(feats))
         return bbox2result(det_bboxes, det_labels, self.bbox_head[-1].num_classes)
 
 
@@ -698,6 +853,43 @@ class HybridTaskCascade(CascadeRCNN):
                 else head.conv_features(mask_feats)
             probs.append(head.get_mask_probs(head.upsample_features(last), det_labels))
         return sum(probs) / float(len(probs))
+
+    def aug_test(self, imgs, img_metas, proposals=None, rescale=False):
+        """htc.py:441-561 with ``keep_all_stages=False``: each view's semantic feature and stage loop, merged boxes
+        and scores, then the mask ensemble of every stage on every view (``mask_roi_extractor[-1]`` + semantic
+        fusion, mask information flow) merged over the A x stages entries, ordered by view and then by stage ->
+        ``(bbox_results, probs [k, 28, 28])``.  ``rescale`` is ignored: the boxes are in the original image scale
+        (htc.py:506).  ``proposals``: merged ``[(props, valid)]`` in the original scale instead of the RPN."""
+        from .post_processing import bbox2result
+        det_bboxes, det_labels, masks = self.aug_test_dets(imgs, img_metas, proposals)
+        return bbox2result(det_bboxes, det_labels, self.bbox_head[-1].num_classes), masks
+
+    def aug_test_dets(self, imgs, img_metas, proposals=None):
+        """-> ``(det_bboxes [k,5], det_labels [k], mask_probs [k,28,28])`` device tensors, original image scale."""
+        from . import functional as BF
+        from .merge_augs import merge_aug_masks
+        if self.test_cfg.get('keep_all_stages', False):
+            raise NotImplementedError('keep_all_stages=True (per-stage results) is not built')
+        self._check_aug(img_metas)
+        feats = self.extract_feats(imgs)
+        semantic_feats = [self.semantic_head(x)[1] if self.with_semantic else None for x in feats]
+        det_bboxes, det_labels = self._aug_test_dets(feats, img_metas, proposals, semantic_feats)
+        if det_bboxes.shape[0] == 0:
+            return det_bboxes, det_labels, det_bboxes.new_zeros((0, 28, 28))
+        rois_all = BF.aug_map_boxes([det_bboxes[:, :4]] * len(feats), self._view_geoms(img_metas), back=False,
+                                    mode='rois')
+        probs, entry_metas = [], []
+        ext = self.mask_roi_extractor[-1]
+        for a, (x, meta) in enumerate(zip(feats, img_metas)):
+            mask_feats = self._fused_roi_feats(ext, x, rois_all[a], semantic_feats[a], 'mask')
+            last = None
+            for i in range(self.num_stages):
+                head = self.mask_head[i]
+                last = head.res_features(mask_feats, last) if self.mask_info_flow \
+                    else head.conv_features(mask_feats)
+                probs.append(head.get_mask_probs(head.upsample_features(last), det_labels))
+                entry_metas.append(meta)
+        return det_bboxes, det_labels, merge_aug_masks(probs, entry_metas, self.test_cfg.rcnn)
 
 
 @DETECTORS.register_module

@@ -1856,6 +1856,125 @@ def gather_boxes(flat, idx, scores):
 
 
 # ----------------------------------------------------------------------------------------
+# test-time augmentation: box mapping and the merges of aug_test (csrc/aug_merge.hip)
+# ----------------------------------------------------------------------------------------
+AUG_MAX_VIEWS = 16
+AUG_MAX_MASK_ENTRIES = 64
+_AUG_MAP_MODES = {'boxes': 0, 'rois': 1, 'nms': 2}
+
+
+def _aug_geoms(geoms):
+    """``[(scale_factor, flip, W), ...]`` -> the three HOST arrays of the C ABI."""
+    for s, _, _ in geoms:
+        if not isinstance(s, float):
+            raise NotImplementedError('aug_test takes a float scale_factor (keep_ratio=True); got %r' % (s,))
+    return (_c_float_array([g[0] for g in geoms]), _c_int_array([1 if g[1] else 0 for g in geoms]),
+            _c_int_array([int(g[2]) for g in geoms]))
+
+
+def aug_map_boxes(srcs, geoms, back=False, mode='boxes', valids=None):
+    """``bbox_mapping`` / ``bbox_mapping_back`` for A views in one launch (``bgs_aug_map_boxes``).
+
+    ``srcs``: A float32 ``[n, cols]`` tensors (the same tensor A times maps one set into every view) whose first
+    ``4 * nbox`` columns are boxes; ``geoms``: A ``(scale_factor, flip, W)`` triples.
+    ``mode='boxes'``: ``[A, n, 4 * nbox]`` (``nbox = cols // 4``); ``'rois'``: ``[A, n, 5]`` rows ``(0, box)``;
+    ``'nms'`` (``cols == 5``): ``(rows [A * n, 5], scores [A * n], count [1] int32)`` — the concatenated proposals of
+    ``merge_aug_proposals`` with score -1 in the rows whose ``valids[a]`` entry is False."""
+    _require_cuda(*srcs)
+    A = len(srcs)
+    if A != len(geoms) or A == 0:
+        raise ValueError('one (scale_factor, flip, W) triple per view')
+    if A > AUG_MAX_VIEWS:
+        raise NotImplementedError('bgs_aug_map_boxes: at most %d views (got %d)' % (AUG_MAX_VIEWS, A))
+    code = _AUG_MAP_MODES[mode]
+    srcs = [s if s.dtype == torch.float32 and s.is_contiguous() else _f32c(s) for s in srcs]
+    n, cols = srcs[0].shape
+    assert all(s.shape == (n, cols) for s in srcs)
+    dev = srcs[0].device
+    nbox = cols // 4 if code == 0 else 1
+    out_scores = count = None
+    if code == 0:
+        out = torch.empty((A, n, 4 * nbox), dtype=torch.float32, device=dev)
+    elif code == 1:
+        out = torch.empty((A, n, 5), dtype=torch.float32, device=dev)
+    else:
+        assert cols == 5
+        if A * n > 4096:
+            raise NotImplementedError('merged proposals: A x max_num <= 4096 (bgs_nms_batched); got %d' % (A * n))
+        out = torch.empty((A * n, 5), dtype=torch.float32, device=dev)
+        out_scores = torch.empty((A * n,), dtype=torch.float32, device=dev)
+        count = torch.empty((1,), dtype=torch.int32, device=dev)
+    vals = None
+    if valids is not None:
+        valids = [v.view(torch.uint8) if v.dtype == torch.bool else v.to(torch.uint8) for v in valids]
+        valids = [v.contiguous() for v in valids]
+        assert len(valids) == A and all(v.numel() == n for v in valids)
+        _require_cuda(*valids)
+        vals = _c_ptr_array(valids)
+    sc, fl, wd = _aug_geoms(geoms)
+    rc = capi.load().bgs_aug_map_boxes(_c_ptr_array(srcs), vals, A, n, cols, nbox, sc, fl, wd, 1 if back else 0,
+                                       code, capi.ptr(out), None if out_scores is None else capi.ptr(out_scores),
+                                       None if count is None else capi.ptr(count), capi.current_stream(dev))
+    capi.check('bgs_aug_map_boxes', rc)
+    if code == 2:
+        return out, out_scores, count
+    return out
+
+
+def _aligned(t):
+    t = t if t.dtype == torch.float32 and t.is_contiguous() else _f32c(t)
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def aug_merge_bboxes(boxes, scores, geoms, valid=None):
+    """``merge_aug_bboxes`` in one launch (``bgs_aug_merge_bboxes``): A views of ``boxes [n, 4k]`` (view scale, not
+    yet mapped back) and ``scores [n, C]`` -> ``(mean of the mapped-back boxes, mean of the scores)``; sums in view
+    order, then / A.  ``valid [n]``: rows where it is False get score -1 (the padding of the proposal list)."""
+    _require_cuda(*boxes, *scores)
+    A = len(boxes)
+    if A != len(scores) or A != len(geoms) or A == 0:
+        raise ValueError('one boxes / scores / (scale_factor, flip, W) per view')
+    if A > AUG_MAX_VIEWS:
+        raise NotImplementedError('bgs_aug_merge_bboxes: at most %d views (got %d)' % (AUG_MAX_VIEWS, A))
+    boxes = [_aligned(b) for b in boxes]
+    scores = [_aligned(s) for s in scores]
+    n, bc = boxes[0].shape
+    C = scores[0].shape[1]
+    assert all(b.shape == (n, bc) for b in boxes) and all(s.shape == (n, C) for s in scores)
+    dev = boxes[0].device
+    out_b = torch.empty((n, bc), dtype=torch.float32, device=dev)
+    out_s = torch.empty((n, C), dtype=torch.float32, device=dev)
+    if valid is not None:
+        valid = (valid.view(torch.uint8) if valid.dtype == torch.bool else valid.to(torch.uint8)).contiguous()
+        assert valid.numel() == n
+    sc, fl, wd = _aug_geoms(geoms)
+    rc = capi.load().bgs_aug_merge_bboxes(_c_ptr_array(boxes), _c_ptr_array(scores), A, n, bc, C, sc, fl, wd,
+                                          None if valid is None else capi.ptr(valid), capi.ptr(out_b),
+                                          capi.ptr(out_s), capi.current_stream(dev))
+    capi.check('bgs_aug_merge_bboxes', rc)
+    return out_b, out_s
+
+
+def aug_merge_masks(masks, flips):
+    """``merge_aug_masks`` without weights in one launch (``bgs_aug_merge_masks``): M ``[k, 28, 28]`` probability
+    tensors, entry m mirrored along x where ``flips[m]`` -> their mean (sum in entry order, then / M)."""
+    _require_cuda(*masks)
+    M = len(masks)
+    if M != len(flips) or M == 0:
+        raise ValueError('one flip flag per mask entry')
+    if M > AUG_MAX_MASK_ENTRIES:
+        raise NotImplementedError('bgs_aug_merge_masks: at most %d entries (got %d)' % (AUG_MAX_MASK_ENTRIES, M))
+    masks = [_aligned(m) for m in masks]
+    k, S, S2 = masks[0].shape
+    assert S == S2 and all(m.shape == (k, S, S) for m in masks)
+    out = torch.empty((k, S, S), dtype=torch.float32, device=masks[0].device)
+    rc = capi.load().bgs_aug_merge_masks(_c_ptr_array(masks), _c_int_array([1 if f else 0 for f in flips]), M, k, S,
+                                         capi.ptr(out), capi.current_stream(masks[0].device))
+    capi.check('bgs_aug_merge_masks', rc)
+    return out
+
+
+# ----------------------------------------------------------------------------------------
 # fused target assignment / RPN loss / proposal decode / RoI targets (csrc/det_targets.hip)
 # ----------------------------------------------------------------------------------------
 def _c_int_array(vals):

@@ -581,6 +581,39 @@ int bgs_soft_nms_batched(const float* dets, const int* counts, int P, int nmax, 
                          bgs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Test-time augmentation (flip / multi-scale aug_test), one launch each, no workspace.  A <= 16 views; per view a
+ *   HOST triple (scale s > 0, flip, width W = img_shape[1] of that view), passed to the kernel by value.
+ *   Arithmetic is the float32 CPU one, bit for bit, with no FMA contraction:
+ *     forward (bbox_mapping, mmdet/core/bbox/transforms.py:133-138): b * s, then if flip
+ *       x1' = (W - x2) - 1, x2' = (W - x1) - 1 (bbox_flip, :114-130);
+ *     back (bbox_mapping_back, :141-146): the flip first, then b / s (IEEE division).
+ * bgs_aug_map_boxes: host_src [A] device pointers to [n, src_cols] rows whose first 4 * nbox columns are nbox boxes
+ *   (one pointer repeated A times maps one set into every view); back 0 = forward, 1 = back.
+ *   out_mode 0: out [A, n, 4 * nbox] mapped boxes;
+ *   out_mode 1 (nbox = 1): out [A, n, 5] RoI rows (0, x1, y1, x2, y2) for each view's RoI extractor
+ *     (aug_test_bboxes / aug_test_mask, mmdet/models/detectors/test_mixins.py:146-150, :220-223);
+ *   out_mode 2 (nbox = 1, src_cols >= 5, A * n <= 4096): the concatenated problem of merge_aug_proposals
+ *     (mmdet/core/post_processing/merge_augs.py:27-36): out [A * n, 5] = (mapped box, score), score -1 where
+ *     host_valid[a][row] == 0 (host_valid NULL or an entry NULL: every row valid); out_scores [A * n] (or NULL) the
+ *     same scores; out_count [1] (or NULL) the number of valid rows.
+ * bgs_aug_merge_bboxes: merge_aug_bboxes (merge_augs.py:45-72): out_boxes [n, box_cols] = mean over the views of the
+ *   mapped-back host_boxes[a] [n, box_cols] (box_cols % 4 == 0: 4 * classes or 4), out_scores [n, C] = mean of
+ *   host_scores[a] [n, C]; sums in view order, then / A; rows with valid[row] == 0 get score -1 (valid may be NULL).
+ *   Every pointer 16-byte aligned (BGS_ERR_INVALID_ARG otherwise).
+ * bgs_aug_merge_masks: merge_aug_masks without weights (merge_augs.py:83-98; htc.py:517-548 with A x stages
+ *   entries): out [k, size, size] = (sum over entries in order of host_masks[m], mirrored along x where
+ *   host_flip[m]) / M.  size == 28 only, M <= 64, pointers 16-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+int bgs_aug_map_boxes(const float* const* host_src, const unsigned char* const* host_valid, int A, int n,
+                      int src_cols, int nbox, const float* host_scale, const int* host_flip, const int* host_width,
+                      int back, int out_mode, float* out, float* out_scores, int* out_count, bgs_stream_t stream);
+int bgs_aug_merge_bboxes(const float* const* host_boxes, const float* const* host_scores, int A, int n, int box_cols,
+                         int C, const float* host_scale, const int* host_flip, const int* host_width,
+                         const unsigned char* valid, float* out_boxes, float* out_scores, bgs_stream_t stream);
+int bgs_aug_merge_masks(const float* const* host_masks, const int* host_flip, int M, int k, int size, float* out,
+                        bgs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Target assignment without the [G, A] IoU matrix.  Replaces MaxIoUAssigner.assign /
  *   assign_wrt_overlaps (mmdet/core/bbox/assigners/max_iou_assigner.py:47-180, incl. its CPU
  *   fallback for > 50 GTs and the Python loop over GTs) and bbox_overlaps

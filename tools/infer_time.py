@@ -5,6 +5,8 @@ batched NMS, max 300 dets) — informational, not the headline metric.
     python tools/infer_time.py [iters]
     python tools/infer_time.py --nms soft_nms [iters]    # simple_test with the configs' commented soft-NMS setting
                                                          # (iou_thr 0.5, min_score 0.05) next to hard NMS
+    python tools/infer_time.py --aug flip [iters]        # aug_test: the image and its flip (A = 2)
+    python tools/infer_time.py --aug ms2flip [iters]     # aug_test: 800 x 1344 and 960 x 1600, each with its flip (A = 4)
 """
 import os
 import sys
@@ -63,9 +65,39 @@ def soft_vs_hard(model, img, metas, iters):
     print(json.dumps(dict(out, soft_nms_cfg=SOFT_NMS, iters=iters)))
 
 
+def _aug_views(kind, dev):
+    """(imgs, img_metas) of ``aug_test``: the 800 x 1333 image (padded 800 x 1344), its flip, and for ``ms2flip`` a
+    960 x 1600 view (scale 1.2, padded 960 x 1600) with its flip."""
+    scales = [(800, 1333, 800, 1344, 1.0)] + ([(960, 1600, 960, 1600, 1.2)] if kind == 'ms2flip' else [])
+    imgs, metas = [], []
+    for h, w, ph, pw, s in scales:
+        for flip in (False, True):
+            imgs.append(torch.randn(1, 3, ph, pw, device=dev))
+            metas.append([dict(img_shape=(h, w, 3), pad_shape=(ph, pw, 3), ori_shape=(800, 1333, 3),
+                               scale_factor=s, flip=flip)])
+    return imgs, metas
+
+
+def aug_vs_simple(model, kind, iters, dev):
+    """aug_test ms per image next to simple_test on the same model and (first) image."""
+    import json
+    imgs, metas = _aug_views(kind, dev)
+    with torch.no_grad():
+        ms_simple, _ = _time(lambda: model(imgs[0], metas[0], return_loss=False, rescale=True), iters)
+        ms_aug, res = _time(lambda: model(imgs, metas, return_loss=False, rescale=True), iters)
+    print(json.dumps(dict(aug=kind, views=len(imgs), simple_test_ms_per_img=round(ms_simple, 3),
+                          aug_test_ms_per_img=round(ms_aug, 3), dets=sum(r.shape[0] for r in res), iters=iters)))
+
+
 def main():
     argv = sys.argv[1:]
     nms = 'nms'
+    aug = None
+    if '--aug' in argv:
+        k = argv.index('--aug')
+        aug = argv[k + 1]
+        del argv[k:k + 2]
+        assert aug in ('flip', 'ms2flip'), aug
     if '--nms' in argv:
         k = argv.index('--nms')
         nms = argv[k + 1]
@@ -87,6 +119,8 @@ def main():
                   scale_factor=1.0, flip=False)]
     if nms == 'soft_nms':
         return soft_vs_hard(model, img, metas, iters)
+    if aug is not None:
+        return aug_vs_simple(model, aug, iters, dev)
     for _ in range(3):
         res = model(img, metas, return_loss=False, rescale=True)
     torch.cuda.synchronize()
