@@ -18,7 +18,7 @@
 //     nearest-2x-upsampled coarser map of the FPN top-down path), then the clamp — 16-byte loads / stores.
 // k steps ascend and the six plane products of a step come in the ring kernel's order, so every output is BIT-IDENTICAL to
 // conv_igemm_bfx_dma_kernel / conv1x1_bfx_wide_kernel (tests/test_gpu_det_ops.py).  LDS 51 KB, <= 168 VGPRs: three
-// workgroups per CU.  Eligible: 1x1 / stride 1 or 2 / no padding, Cin % 64 == 0, Cout % 256 == 0, no split-K, no ReLU mask,
+// workgroups per CU.  Eligible: 1x1 / stride 1 or 2 / no padding, Cin % 64 == 0, Cout % 128 == 0, no split-K,
 // tensors below 2 GB (32-bit buffer offsets).
 #include <stdlib.h>
 
@@ -56,8 +56,8 @@ struct PlanesArgs {
   int KC;                // K / 16
 };
 
-// ABL: timing-only ablations (tools/planes_ablate.py; results are WRONG for ABL != 0): 1 = filter fragments loaded once,
-// 2 = activation tile loaded once, 4 = no output stores, 8 = no MFMAs
+// ABL (only instantiated != 0 under -DBGS_ABLATE, tools/planes_ablate.py): timing-only ablations, results are WRONG:
+// 1 = filter fragments loaded once, 2 = activation tile loaded once, 4 = no output stores, 8 = no MFMAs
 // NB: 32-channel fragments per wave: 2 = 256 output channels per workgroup, 1 = 128 (the 128-channel layers, and the
 // 256-channel layers on the small maps whose 64-pixel tiles alone leave half the CUs without a workgroup)
 template <int ABL, int NB>
@@ -329,17 +329,18 @@ int bgs_internal_conv1x1_planes(const bgs_conv::ConvArgs& pc, const void* wsplit
   g.c.tiles_n = p.Cout / (128 * nb);
   g.c.chunk = (g.c.tiles_m * g.c.tiles_n + 7) / 8;
   g.c.partial = nullptr;
-  static int abl = -1;                      // BGS_BFX_PLANES_ABLATE: timing-only, see the kernel's ABL
-  if (abl < 0) {
-    const char* e = getenv("BGS_BFX_PLANES_ABLATE");
-    abl = e ? atoi(e) : 0;
-  }
   const dim3 grid((unsigned)(8 * g.c.chunk)), block(kThreads);
 #define BGS_PL(A_) \
   do { \
     if (nb == 2) hipLaunchKernelGGL((conv1x1_planes_bfx_kernel<A_, 2>), grid, block, 0, st, g); \
     else hipLaunchKernelGGL((conv1x1_planes_bfx_kernel<A_, 1>), grid, block, 0, st, g); \
   } while (0)
+#ifdef BGS_ABLATE
+  static int abl = -1;                      // BGS_BFX_PLANES_ABLATE: timing-only, see the kernel's ABL
+  if (abl < 0) {
+    const char* e = getenv("BGS_BFX_PLANES_ABLATE");
+    abl = e ? atoi(e) : 0;
+  }
   switch (abl) {
     case 1: BGS_PL(1); break;
     case 2: BGS_PL(2); break;
@@ -351,6 +352,9 @@ int bgs_internal_conv1x1_planes(const bgs_conv::ConvArgs& pc, const void* wsplit
     case 15: BGS_PL(15); break;
     default: BGS_PL(0); break;
   }
+#else
+  BGS_PL(0);
+#endif
 #undef BGS_PL
   g_planes_last = nb;
   bgs_internal_census_bump(BGS_CENSUS_PLANES_1X1);

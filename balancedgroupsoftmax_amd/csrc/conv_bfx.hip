@@ -833,8 +833,11 @@ __global__ __launch_bounds__(256) void bfx_split_weights_dgrad_kernel(const floa
 // 16 channels) are split ONCE per channel chunk into three bf16 planes in LDS and shared by the
 // nine taps — the split cost and the A traffic drop 9x; only the pre-split filter slice streams
 // per tap (contiguous 4 KB runs per plane).  A is single-buffered (one extra barrier per chunk),
-// B double-buffered: 62.8 KB of LDS -> two workgroups per CU.  gridDim.z slices the channel chunks
-// (split-K for the small maps); partial slabs go through the shared split-K epilogue.
+// B double-buffered.  gridDim.z slices the channel chunks (split-K for the small maps); partial
+// slabs go through the shared split-K epilogue.
+// (The first version — 48-byte filter rows, a per-step tap division, 62.8 KB of LDS -> two workgroups
+//  per CU — was 3 - 24 % behind variant 2 on every 3x3 layer of cfg[1] but the smallest (0.027 vs 0.028 ms),
+//  profiles/r2g_bfx_sweep.txt: removed.)
 constexpr int TH = 8, TW = 16, PH = TH + 2, PW = TW + 2, PROWS = PH * PW;   // 180 patch pixels
 constexpr int HLDR = 48;                                                    // LDS row stride, bytes
 constexpr int AQ = PROWS * 4;                                               // fp32 quads per patch
@@ -915,197 +918,11 @@ __device__ __forceinline__ void halo_store_tile_lds(const ConvArgs& p, const f32
   }
 }
 
-template <int NB>
-__global__ __launch_bounds__(kThreads, 2) void conv3x3_halo_bfx_kernel(HaloBfxArgs q) {
-  const ConvArgs& p = q.c;
-  constexpr int BN = 64 * NB;
-  constexpr int A_PLANE = PROWS * HLDR, B_PLANE = BN * HLDR;
-  constexpr int A_BYTES = 3 * A_PLANE, B_BUF = 3 * B_PLANE;
-  constexpr int NPIECE = 3 * BN * 2;
-  constexpr int PB = (NPIECE + kThreads - 1) / kThreads;
-  __shared__ __attribute__((aligned(16))) unsigned char lds[A_BYTES + 2 * B_BUF];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int vtile = p.chunk ? (int)((blockIdx.x & 7) * p.chunk + (blockIdx.x >> 3)) : (int)blockIdx.x;
-  if (vtile >= p.tiles_m * p.tiles_n) return;                  // workgroup-uniform
-  const int tm = vtile / p.tiles_n, tn = vtile - tm * p.tiles_n;
-  const int n = tm / (q.tiles_y * q.tiles_x);
-  const int trem = tm - n * (q.tiles_y * q.tiles_x);
-  const int ty = trem / q.tiles_x, tx = trem - ty * q.tiles_x;
-  const int h0 = ty * TH - 1, w0 = tx * TW - 1;                // input coords of patch (0, 0)
-  const int n0 = tn * BN;
-  const int cchunks = p.Cin / 16;
-  const int c_begin = p.partial ? blockIdx.z * q.chunks_per_split : 0;
-  const int c_end = p.partial ? min(cchunks, c_begin + q.chunks_per_split) : cchunks;
-
-  // ---- staging roles.  A: patch quads idx = tid + 256 i; prow = idx / 4, kq = idx % 4
-  const float* a_src[AQT];
-  int a_dst[AQT];
-  bool a_use[AQT], a_in[AQT];
-#pragma unroll
-  for (int i = 0; i < AQT; ++i) {
-    const int idx = tid + kThreads * i;
-    a_use[i] = idx < AQ;
-    const int prow = a_use[i] ? idx >> 2 : 0, kq = idx & 3;
-    const int pr = prow / PW, pc = prow - pr * PW;
-    const int hi = h0 + pr, wi = w0 + pc;
-    a_in[i] = a_use[i] && hi >= 0 && hi < p.H && wi >= 0 && wi < p.W;
-    a_src[i] = p.x + (((size_t)n * p.H + (a_in[i] ? hi : 0)) * p.W + (a_in[i] ? wi : 0)) * p.Cin + kq * 4;
-    a_dst[i] = prow * HLDR + kq * 8;
-  }
-  // B: piece id = tid + 256 i -> (plane, row, half)
-  const __bf16* b_src[PB];
-  int b_dst[PB];
-  bool b_use[PB], b_ok[PB];
-#pragma unroll
-  for (int i = 0; i < PB; ++i) {
-    const int id = tid + kThreads * i;
-    b_use[i] = id < NPIECE;
-    const int idc = b_use[i] ? id : 0;
-    const int plane = idc / (BN * 2);
-    const int rem = idc - plane * (BN * 2);
-    const int row = rem >> 1, half = rem & 1;
-    b_ok[i] = b_use[i] && (n0 + row < p.Cout);
-    b_src[i] = q.ws + ((size_t)plane * q.KC * p.Cout + (b_ok[i] ? n0 + row : 0)) * 16 + half * 8;
-    b_dst[i] = A_BYTES + plane * B_PLANE + row * HLDR + half * 16;
-  }
-
-  f32x4 ra[AQT];
-  u32x4 rb[PB];
-  auto load_a = [&](int chunk) {
-#pragma unroll
-    for (int i = 0; i < AQT; ++i) {
-      const float* src = a_in[i] ? a_src[i] + chunk * 16 : reinterpret_cast<const float*>(g_zero_page);
-      ra[i] = *reinterpret_cast<const f32x4*>(src);
-    }
-  };
-  auto store_a = [&]() {
-#pragma unroll
-    for (int i = 0; i < AQT; ++i) {
-      if (!a_use[i]) continue;
-      u32x2 h, m, l;
-      split3(ra[i], h, m, l);
-      unsigned char* d = lds + a_dst[i];
-      *reinterpret_cast<u32x2*>(d) = h;
-      *reinterpret_cast<u32x2*>(d + A_PLANE) = m;
-      *reinterpret_cast<u32x2*>(d + 2 * A_PLANE) = l;
-    }
-  };
-  auto load_b = [&](int chunk, int tap) {
-    const size_t koff = (size_t)(tap * cchunks + chunk) * p.Cout * 16;
-#pragma unroll
-    for (int i = 0; i < PB; ++i) {
-      const __bf16* src = b_ok[i] ? b_src[i] + koff : reinterpret_cast<const __bf16*>(g_zero_page);
-      rb[i] = *reinterpret_cast<const u32x4*>(src);
-    }
-  };
-  auto store_b = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < PB; ++i)
-      if (b_use[i]) *reinterpret_cast<u32x4*>(lds + buf * B_BUF + b_dst[i]) = rb[i];
-  };
-
-  // ---- fragment roles: lane frow of sub-tile a owns pixel m = 64 wm + 32 a + frow
-  const int frow = lane & 31, fk = lane >> 5;
-  int a_frag[2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-    const int m = wm * 64 + a * 32 + frow;
-    a_frag[a] = ((m >> 4) * PW + (m & 15)) * HLDR + fk * 16;      // patch row of tap (0, 0)
-  }
-  const int b_frag = A_BYTES + (wn * 32 * NB + frow) * HLDR + fk * 16;
-
-  f32x16 acc[2][NB];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < NB; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-  const int nsteps = (c_end - c_begin) * 9;
-  load_a(c_begin);
-  load_b(c_begin, 0);
-  store_a();
-  store_b(0);
-  __syncthreads();
-  int chunk = c_begin, tap = 0;
-  for (int t = 0; t < nsteps; ++t) {
-    const int bbuf = t & 1;
-    const bool more = t + 1 < nsteps;
-    int nchunk = chunk, ntap = tap + 1;
-    if (ntap == 9) {
-      ntap = 0;
-      ++nchunk;
-    }
-    if (more) load_b(nchunk, ntap);                             // next filter slice in flight
-    const bool next_a = tap == 0 && chunk + 1 < c_end;
-    if (next_a) load_a(chunk + 1);                              // next patch: held in registers
-
-    const int tap_off = ((tap / 3) * PW + (tap % 3)) * HLDR;
-    bf16x8 fa[3][2], fb[3][NB];
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-        fa[s][a] = *reinterpret_cast<const bf16x8*>(lds + a_frag[a] + tap_off + s * A_PLANE);
-#pragma unroll
-      for (int b = 0; b < NB; ++b)
-        fb[s][b] = *reinterpret_cast<const bf16x8*>(lds + bbuf * B_BUF + b_frag + s * B_PLANE + b * 32 * HLDR);
-    }
-#pragma unroll
-    for (int tt = 2; tt >= 0; --tt)
-#pragma unroll
-      for (int i = 0; i <= tt; ++i)
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-          for (int b = 0; b < NB; ++b)
-            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][a], fb[tt - i][b], acc[a][b],
-                                                                0, 0, 0);
-    if (more) store_b(bbuf ^ 1);
-    __syncthreads();
-    if (tap == 8 && chunk + 1 < c_end) {                        // every wave is done with patch `chunk`
-      store_a();
-      __syncthreads();
-    }
-    tap = ntap;
-    chunk = nchunk;
-  }
-
-  // ---- epilogue: C/D layout col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-  float* part = p.partial ? p.partial + (size_t)blockIdx.z * p.M * p.Cout : nullptr;
-#pragma unroll
-  for (int a = 0; a < 2; ++a) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int i = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      const int m = wm * 64 + a * 32 + i;
-      const int ho = ty * TH + (m >> 4), wo = tx * TW + (m & 15);
-      if (ho >= p.H || wo >= p.W) continue;
-      const size_t row = (((size_t)n * p.H + ho) * p.W + wo) * p.Cout;
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const int j = n0 + wn * 32 * NB + b * 32 + (lane & 31);
-        if (j >= p.Cout) continue;
-        float v = acc[a][b][r];
-        if (part) {
-          part[row + j] = v;
-        } else {
-          if (p.bias) v += p.bias[j];
-          if (p.relu) v = fmaxf(v, 0.f);
-          p.y[row + j] = v;
-        }
-      }
-    }
-  }
-}
-
-// Variant 2 (default): the same data flow with (i) the nine taps of a chunk fully unrolled — the
-// tap's patch offset is an immediate of the ds_read, no per-step integer division — and (ii) the
-// filter slices stored UNPADDED (32-byte rows) with the two 16-byte halves of a row swapped on odd
-// 8-row groups (conflict-free ds_read_b128 without padding): 50.5 KB of LDS and <= 168 VGPRs ->
+// Variant 2 (the register-staged reference of the tests): the data flow above with (i) the nine
+// taps of a chunk fully unrolled — the tap's patch offset is an immediate of the ds_read, no
+// per-step integer division — and (ii) the filter slices stored UNPADDED (32-byte rows) with the
+// two 16-byte halves of a row swapped on odd 8-row groups (conflict-free ds_read_b128 without
+// padding): 50.5 KB of LDS and <= 168 VGPRs ->
 // THREE workgroups per CU.  Measured on the P2 layer (profiles/r2f_pmc_bfx_halo_raw.txt): with two
 // workgroups per CU the matrix pipe is busy 49 % of the time — the four waves of a workgroup sit
 // on four SIMDs, each shared with ONE wave of another workgroup, and every barrier couples them;
@@ -1331,9 +1148,8 @@ __global__ __launch_bounds__(kThreads, 3) void conv3x3_halo_bfx3_kernel(HaloBfxA
 // layer's epilogue was built and measured too — no faster, 1.5x the activation bytes: removed.
 // LDS: 24 KB filter double buffer + 1 KB scratch (dummy pieces) + 16.9 KB patch (8 x 16 tile; 25.3 KB otherwise).
 // (NS = 1: the bf16 mode — hi planes only, one MFMA per product.)
-// PF (variant 5): the A fragments of tap t + 1 are read from the patch DURING tap t's MFMAs — the
-// patch does not change inside a channel chunk, so those reads need not sit behind the step's
-// barrier; after the barrier only the six filter fragments remain between a wave and its MFMAs.
+// (Tried and removed: the A fragments of tap t + 1 read from the patch DURING tap t's MFMAs, across the step's
+//  barrier: 3.054 -> 3.110 ms over the 3x3 layers of a forward, profiles/r5d_halo_pf_ab.txt.)
 // GTH x GTW: the pixel tile (<= 128 pixels; the MFMA rows beyond GTH * GTW are padding: they read patch pixel
 // (0, 0) and are never stored).  8 x 16 everywhere but on the small maps, where the tile that wastes the fewest
 // rows is chosen per layer (halo_bfx_geom: 50 x 84 -> 10 x 12: 35 tiles per image instead of 42; 25 x 42 -> 5 x 21:
@@ -1344,7 +1160,7 @@ __global__ __launch_bounds__(kThreads, 3) void conv3x3_halo_bfx3_kernel(HaloBfxA
 // 12 KB filter slice per workgroup and tap itself (timing-only ablation: 0.77 ms with it, 0.52 ms without) — on
 // either path: a variant whose waves load their filter fragments straight from global memory into the MFMA's
 // registers (no filter LDS, no DMA, ONE barrier per channel chunk instead of ten, bit-identical) was 4.5 % slower.
-template <int NB, int NS = 3, bool PF = false, int GTH = 8, int GTW = 16, bool PADDED = false>
+template <int NB, int NS = 3, int GTH = 8, int GTW = 16>
 __global__ __launch_bounds__(kThreads, 3) void conv3x3_halo_bfx4_kernel(HaloBfxArgs q) {
   const ConvArgs& p = q.c;
   constexpr int TH = GTH, TW = GTW, PH = TH + 2, PW = TW + 2, PROWS = PH * PW;      // (shadow the 8 x 16 default)
@@ -1362,8 +1178,9 @@ __global__ __launch_bounds__(kThreads, 3) void conv3x3_halo_bfx4_kernel(HaloBfxA
   // other tiles) are conflict-free for 32 CONSECUTIVE pixels but not across the 18-pixel row wrap: every group
   // 2-way, 24 of a wave's 72 LDS cycles per step — the 34 % SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE of
   // profiles/r5_pmc_final_tree.md — and the ds_write_b64 of the split (four pixels = 192 bytes per 16 lanes) was
-  // 2-way as well; 32-byte pixels make that store one 128-byte window per lane group.
-  constexpr bool SWZ = GTH == 8 && GTW == 16 && !PADDED;      // (PADDED: the 48-byte rows on the 8 x 16 tile, A/B only)
+  // 2-way as well; 32-byte pixels make that store one 128-byte window per lane group (3.022 -> 2.988 ms over the 3x3
+  // layers of a forward, profiles/r8h_halo_lds_layout_ring3_dma_ablation.txt).
+  constexpr bool SWZ = GTH == 8 && GTW == 16;
   constexpr int HL = SWZ ? 32 : HLDR;
   constexpr int A_PLANE = PROWS * HL;
   constexpr int OPER_BYTES = A_OFF + NS * A_PLANE, EPI_BYTES = 64 * (BN + 4) * 4;   // operands | epilogue tile
@@ -1492,7 +1309,6 @@ __global__ __launch_bounds__(kThreads, 3) void conv3x3_halo_bfx4_kernel(HaloBfxA
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   int cur = 0, nxt = B_BUF;                                      // byte offsets of the two B buffers
-  bf16x8 fa_next[NS][2];
   for (int chunk = c_begin; chunk < c_end; ++chunk) {
     const bool last_chunk = chunk + 1 >= c_end;
 #pragma unroll
@@ -1514,22 +1330,11 @@ __global__ __launch_bounds__(kThreads, 3) void conv3x3_halo_bfx4_kernel(HaloBfxA
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
 #pragma unroll
-        for (int a = 0; a < 2; ++a) {
-          if (PF && tap > 0) fa[s][a] = fa_next[s][a];
-          else fa[s][a] = *reinterpret_cast<const bf16x8*>(lds + a_frag[a][tap_par] + tap_off + s * A_PLANE);
-        }
+        for (int a = 0; a < 2; ++a)
+          fa[s][a] = *reinterpret_cast<const bf16x8*>(lds + a_frag[a][tap_par] + tap_off + s * A_PLANE);
 #pragma unroll
         for (int b = 0; b < NB; ++b)
           fb[s][b] = *reinterpret_cast<const bf16x8*>(lds + rd + b_frag + s * B_PLANE + b * 32 * 32);
-      }
-      if (PF && tap < 8) {                                         // tap + 1's patch rows: in flight under the MFMAs
-        const int nxt_off = (((tap + 1) / 3) * PW + ((tap + 1) % 3)) * HL;
-        const int nxt_par = ((tap + 1) / 3 + (tap + 1) % 3) & 1;
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-          for (int a = 0; a < 2; ++a)
-            fa_next[s][a] = *reinterpret_cast<const bf16x8*>(lds + a_frag[a][nxt_par] + nxt_off + s * A_PLANE);
       }
       if (q.flags & 1) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1974,12 +1779,17 @@ __device__ __forceinline__ void halo7_store_tile_lds(const ConvArgs& p, const f3
 }
 
 // ABL (timing-only ablations, results are WRONG; tools/halo_wide_ablate.py): 1 = the second half's A fragments are
-// not read (half 0's are reused), 2 = the patch is staged once and never again, 4 = no filter DMA after the first.
-// FB32 (NS = 3): the filter slice travels as fp32 (the packed fourth section of the split-weight buffer: 8 KB per
-// tap instead of the 12 KB of three bf16 planes) and every wave splits ITS fragment rows in registers in front of
-// the MFMAs (split3 on the same values = the same planes: bit-identical).  Why: the launch is POWER-limited, and what
-// the L2 -> CU path moves costs clock — PMC on the two-round map (profiles/r9b): 1.60 GHz with the filter DMA, 1.95
-// GHz without it (timing-only ablation), while the cycle count moves by 8 % only.
+// not read (half 0's are reused), 2 = the patch is staged once and never again, 4 = no filter DMA after the first;
+// instantiated != 0 under -DBGS_ABLATE only.
+// FB32 (NS = 3; env BGS_HALO_FB32, default off): the filter slice travels as fp32 (the packed fourth section of the
+// split-weight buffer: 8 KB per tap instead of the 12 KB of three bf16 planes) and every wave splits ITS fragment rows
+// in registers in front of the MFMAs (split3 on the same values = the same planes: bit-identical).  Why: the launch is
+// POWER-limited, and what the L2 -> CU path moves costs clock — PMC on the two-round map (profiles/r9b): 1.60 GHz with
+// the filter DMA, 1.95 GHz without it (timing-only ablation), while the cycle count moves by 8 % only.  Measured 6 %
+// SLOWER (88 VALU instructions per step and wave, profiles/r9b_halo_wide_clock_pmc.md).  Still here because taking it
+// out changes the code the compiler emits for the default <3, 0> and <1, 0> instantiations (the FB32 branch in the
+// filter-DMA lambda and the <3, 0, true> sibling both shape it: profiles/halo_arms_retired_kernel_identity_and_bench.txt),
+// so its removal needs a timing run of variant 7, not a comparison of instruction streams.
 template <int NS, int ABL = 0, bool FB32 = false>
 __global__ __launch_bounds__(kThreads, 2) void conv3x3_halo_bfx7_kernel(HaloBfxArgs q) {
   const ConvArgs& p = q.c;
@@ -2194,8 +2004,23 @@ __global__ __launch_bounds__(kThreads, 2) void conv3x3_halo_bfx7_kernel(HaloBfxA
   halo7_store_tile_lds<NS>(p, acc, n, ty, tx, n0, wm, wn, lane, reinterpret_cast<float*>(lds), (q.flags & 32) != 0);
 }
 
+// The halo kernels the dispatcher launches.  Variant 4 by [planes == 1 ? 0 : 1 + pixel tile][nb - 1]: the pixel tile is
+// halo_bfx_geom's 0..2 (the bf16 mode keeps 8 x 16), nb halo_bfx_plan's 1 | 2.
+using HaloKernel = void (*)(HaloBfxArgs);
+const HaloKernel kHalo4[4][2] = {
+    {conv3x3_halo_bfx4_kernel<1, 1>, conv3x3_halo_bfx4_kernel<2, 1>},                    // bf16 mode
+    {conv3x3_halo_bfx4_kernel<1, 3>, conv3x3_halo_bfx4_kernel<2, 3>},                    // 8 x 16 pixels
+    {conv3x3_halo_bfx4_kernel<1, 3, 10, 12>, conv3x3_halo_bfx4_kernel<2, 3, 10, 12>},    // 10 x 12
+    {conv3x3_halo_bfx4_kernel<1, 3, 5, 21>, conv3x3_halo_bfx4_kernel<2, 3, 5, 21>},      // 5 x 21
+};
+// Variant 2 (8 x 16 only) by [planes == 1 ? 0 : 1][nb - 1].
+const HaloKernel kHalo3[2][2] = {
+    {conv3x3_halo_bfx3_kernel<1, 1>, conv3x3_halo_bfx3_kernel<2, 1>},
+    {conv3x3_halo_bfx3_kernel<1, 3>, conv3x3_halo_bfx3_kernel<2, 3>},
+};
+
 int g_halo_last_nb = 0, g_halo_last_splits = 0, g_halo_last_variant = 0;
-int g_halo_force_splits = -1, g_halo_variant = 4, g_halo_pf = 0, g_halo_padded = 0, g_halo_flags = 1;
+int g_halo_force_splits = -1, g_halo_variant = 4, g_halo_flags = 1;      // g_halo_variant: 4 (default) | 2
 // BGS_HALO_NT (A/B, read once): bit 0 = the patch loads, bit 1 = the output stores carry the non-temporal hint — the
 // activations stream through once while every workgroup re-reads the filter slices from L2 (kernel flag bits 4 / 5)
 int g_halo_nt = -1;
@@ -2327,7 +2152,7 @@ int bfx_ring_stages(const BfxKnobs& knobs, long long wgs) {
   return knobs.nst == 4 ? 4 : 3;
 }
 
-int g_ablate = 0;          // -DBGS_ABLATE builds only (tools/ablate.py): component-ablation timing
+int g_ablate = 0;          // component-ablation timing (tools/ablate.py): stays 0 unless built with -DBGS_ABLATE
 
 // tile (MB*10 + NB), K depth per barrier and split-K factor for a layer
 void bfx_plan(long long M, int Cout, int KC, int& tile, int& bk, int& want) {
@@ -2728,21 +2553,21 @@ extern "C" size_t bgs_conv3x3_halo_bfx_workspace_bytes(int N, int H, int W, int 
 }
 
 extern "C" void bgs_conv3x3_halo_bfx_tuning(int splits, int variant) {
-  g_ablate = (variant >> 8) & 0xff;          // timing-only ablation modes (-DBGS_ABLATE builds)
+#ifdef BGS_ABLATE
+  g_ablate = (variant >> 8) & 0xff;          // timing-only ablation modes; bits 8..15 are ignored in every other build
+#endif
   const int variant0 = variant;
   g_halo_geom = ((variant >> 16) & 0xf) - 1; // 0: default pixel tile | 1: 8 x 16 | 2: 10 x 12 | 3: 5 x 21 | 4: fewest tiles
   if (g_halo_geom > 3) g_halo_geom = -1;
   variant &= 0xff;
   g_halo_force_splits = splits;
-  // 1 = first version (2 workgroups / CU), 2 = taps unrolled + 3 workgroups / CU (register-staged
-  // filter slices), 4 (and 0 = the default) = filter slices by LDS-DMA
-  g_halo_variant = variant == 1 ? 1 : (variant == 2 ? 2 : 4);
-  g_halo_pf = variant == 5 ? 1 : 0;        // 5 = variant 4 + A-fragment prefetch across the barrier
+  // 2 = register-staged filter slices (the tests' bit-identity reference), anything else = 4 (the default): filter
+  // slices by LDS-DMA
+  g_halo_variant = variant == 2 ? 2 : 4;
   // bits 20..23: 0 default (= 1) | 1: s_setprio 1 around the MFMA cluster | 2: static priority = hardware wave slot |
   // 8: none (A/B);  -DBGS_ABLATE builds: 4 / 8 drop two / all of the filter-plane DMAs (timing only)
   g_halo_flags = (variant0 >> 20) & 0xf;
   if (g_halo_flags == 0) g_halo_flags = 1;
-  g_halo_padded = variant == 6 ? 1 : 0;    // 6 = variant 4 with the 48-byte patch rows (before the swizzled 32-byte pixels)
   // bits 24..27: 0 leave as is | 1 wide pixel tile off | 2 automatic | 3 every eligible layer
   const int wide = (variant0 >> 24) & 0xf;
   if (wide >= 1 && wide <= 3) g_halo_wide = wide - 1;
@@ -2873,7 +2698,7 @@ extern "C" int bgs_conv3x3_halo_nhwc_f32_bfx_ex(const float* x, const void* wspl
   // planes in LDS, ONE barrier per 32-channel chunk (conv3x3_planes.hip); -1 = not eligible / declined.  Not under a
   // forced slice count / variant / pixel tile (the tuning hook's A/B arms and the tests that assert them).
   bgs_internal_conv3x3_planes_clear_last();
-  if (q.ns == 3 && g_halo_force_splits < 0 && g_halo_variant == 4 && !g_halo_pf && !g_halo_padded && g_halo_geom < 0 && !g_ablate) {
+  if (q.ns == 3 && g_halo_force_splits < 0 && g_halo_variant == 4 && g_halo_geom < 0 && !g_ablate) {
     const int rc = bgs_internal_conv3x3_planes(p, q.ws, q.KC, (hipStream_t)stream);
     if (rc >= 0) {
       g_halo_last_variant = 9;
@@ -2907,8 +2732,8 @@ extern "C" int bgs_conv3x3_halo_nhwc_f32_bfx_ex(const float* x, const void* wspl
   g_halo_last_splits = splits;
   g_halo_last_wide_units = g_halo_last_tail_units = 0;
   // ---- variant 7: whole rounds of 16 x 16-pixel units, then the left-over image rows on variant 4 (8 x 16 units)
-  if (g_halo_variant == 4 && geom == 0 && !g_halo_padded && !g_halo_pf && splits == 1 && nb == 2 && Cout % 128 == 0 &&
-      halo_wide_mode() > 0 && (long long)M * Cin < 0xffffffffLL) {
+  if (g_halo_variant == 4 && geom == 0 && splits == 1 && nb == 2 && Cout % 128 == 0 && halo_wide_mode() > 0 &&
+      (long long)M * Cin < 0xffffffffLL) {
     constexpr int kSlots = 512;                                 // two workgroups per CU
     const int ty7 = (H + 15) / 16, tx7 = (W + 15) / 16;         // (tx7 == q.tiles_x: both tiles are 16 pixels wide)
     const int tn7 = Cout / 128;
@@ -2942,11 +2767,13 @@ extern "C" int bgs_conv3x3_halo_nhwc_f32_bfx_ex(const float* x, const void* wspl
         hipLaunchKernelGGL((conv3x3_halo_bfx7_kernel<3, 0, true>), dim3((unsigned)(8 * qa.c.chunk)), dim3(kThreads), 0, (hipStream_t)stream, qa);
       else if (q.ns == 1)
         hipLaunchKernelGGL((conv3x3_halo_bfx7_kernel<1>), dim3((unsigned)(8 * qa.c.chunk)), dim3(kThreads), 0, (hipStream_t)stream, qa);
+#ifdef BGS_ABLATE
       else if (g_ablate == 1) BGS_W7(1);
       else if (g_ablate == 2) BGS_W7(2);
       else if (g_ablate == 4) BGS_W7(4);
       else if (g_ablate == 6) BGS_W7(6);
       else if (g_ablate == 7) BGS_W7(7);
+#endif
       else BGS_W7(0);
 #undef BGS_W7
       if (rows_a < (long long)N * ty7) {
@@ -2958,62 +2785,27 @@ extern "C" int bgs_conv3x3_halo_nhwc_f32_bfx_ex(const float* x, const void* wspl
         p.chunk = (q.tile_count + 7) / 8;
         g_halo_last_tail_units = q.tile_count;
         bgs_internal_census_bump(BGS_CENSUS_HALO_BFX4);
-        if (q.ns == 1)
-          hipLaunchKernelGGL((conv3x3_halo_bfx4_kernel<2, 1>), dim3((unsigned)(8 * p.chunk)), dim3(kThreads), 0, (hipStream_t)stream, q);
-        else
-          hipLaunchKernelGGL((conv3x3_halo_bfx4_kernel<2, 3>), dim3((unsigned)(8 * p.chunk)), dim3(kThreads), 0, (hipStream_t)stream, q);
+        hipLaunchKernelGGL(kHalo4[q.ns == 1 ? 0 : 1][1], dim3((unsigned)(8 * p.chunk)), dim3(kThreads), 0, (hipStream_t)stream, q);
       }
       BGS_RETURN_LAUNCH_STATUS();
     }
   }
   dim3 grid((unsigned)(8 * p.chunk), 1u, (unsigned)splits);
-  const bool v4 = g_halo_variant == 4;
-  g_halo_last_variant = v4 ? 4 : (g_halo_variant == 1 && q.ns == 3 ? 1 : 2);
-  if (v4) {
+  g_halo_last_variant = g_halo_variant;
+  if (g_halo_variant == 4) {
     q.zero = zero_page_device();
     if (!q.zero) return BGS_ERR_LAUNCH;
     q.flags = g_halo_flags | halo_nt_flags();
     bgs_internal_census_bump(BGS_CENSUS_HALO_BFX4);
-    if (q.ns == 1) {
-      if (nb == 1) hipLaunchKernelGGL((conv3x3_halo_bfx4_kernel<1, 1>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-      else hipLaunchKernelGGL((conv3x3_halo_bfx4_kernel<2, 1>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-    } else if (geom == 1) {
-      if (nb == 1) hipLaunchKernelGGL((conv3x3_halo_bfx4_kernel<1, 3, false, 10, 12>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-      else hipLaunchKernelGGL((conv3x3_halo_bfx4_kernel<2, 3, false, 10, 12>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-    } else if (geom == 2) {
-      if (nb == 1) hipLaunchKernelGGL((conv3x3_halo_bfx4_kernel<1, 3, false, 5, 21>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-      else hipLaunchKernelGGL((conv3x3_halo_bfx4_kernel<2, 3, false, 5, 21>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-    } else if (nb == 1) {
-      hipLaunchKernelGGL((conv3x3_halo_bfx4_kernel<1, 3>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-    } else if (g_halo_padded) {
-      hipLaunchKernelGGL((conv3x3_halo_bfx4_kernel<2, 3, false, 8, 16, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-    } else if (g_halo_pf) {
-      hipLaunchKernelGGL((conv3x3_halo_bfx4_kernel<2, 3, true>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-    } else {
-      hipLaunchKernelGGL((conv3x3_halo_bfx4_kernel<2, 3>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-    }
-  } else if (g_halo_variant == 1 && q.ns == 3) {
-    if (nb == 1)
-      hipLaunchKernelGGL(conv3x3_halo_bfx_kernel<1>, grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-    else
-      hipLaunchKernelGGL(conv3x3_halo_bfx_kernel<2>, grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-  } else {
-    if (q.ns == 1) {
-      if (nb == 1)
-        hipLaunchKernelGGL((conv3x3_halo_bfx3_kernel<1, 1>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-      else
-        hipLaunchKernelGGL((conv3x3_halo_bfx3_kernel<2, 1>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-    } else if (nb == 1) {
-      hipLaunchKernelGGL((conv3x3_halo_bfx3_kernel<1, 3>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
+    hipLaunchKernelGGL(kHalo4[q.ns == 1 ? 0 : 1 + geom][nb - 1], grid, dim3(kThreads), 0, (hipStream_t)stream, q);
 #ifdef BGS_ABLATE
-    } else if (g_ablate) {
+  } else if (g_ablate && q.ns == 3 && nb == 2) {
 #define ABL_H(A_) case A_: hipLaunchKernelGGL((conv3x3_halo_bfx3_kernel<2, 3, A_>), grid, dim3(kThreads), 0, (hipStream_t)stream, q); break;
-      switch (g_ablate) { ABL_H(1) ABL_H(2) ABL_H(3) ABL_H(4) ABL_H(5) ABL_H(6) ABL_H(8) ABL_H(16) ABL_H(18) ABL_H(26) ABL_H(30) ABL_H(14) default: return BGS_ERR_UNSUPPORTED; }
+    switch (g_ablate) { ABL_H(1) ABL_H(2) ABL_H(3) ABL_H(4) ABL_H(5) ABL_H(6) ABL_H(8) ABL_H(16) ABL_H(18) ABL_H(26) ABL_H(30) ABL_H(14) default: return BGS_ERR_UNSUPPORTED; }
 #undef ABL_H
 #endif
-    } else {
-      hipLaunchKernelGGL((conv3x3_halo_bfx3_kernel<2, 3>), grid, dim3(kThreads), 0, (hipStream_t)stream, q);
-    }
+  } else {
+    hipLaunchKernelGGL(kHalo3[q.ns == 1 ? 0 : 1][nb - 1], grid, dim3(kThreads), 0, (hipStream_t)stream, q);
   }
   if (splits > 1) {
     if (hipGetLastError() != hipSuccess) return BGS_ERR_LAUNCH;

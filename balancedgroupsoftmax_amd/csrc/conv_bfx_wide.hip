@@ -420,7 +420,9 @@ int g_wide_nbw = 0;          // 0 auto | 2 (128 x 64 tile) | 4 (128 x 128)
 int g_wide_narrow = 1;       // automatic mode: 0 = never pick the 128 x 64 tile (BGS_BFX_WIDE_NARROW, A/B)
 int g_wide_splitk = -1;      // -1 auto | 1..16
 int g_wide_last = 0;         // bit 0: the wide kernel ran; bits 4..7: NST; bits 8..: K slices
-int g_wide_ablate = 0;       // -DBGS_ABLATE builds only
+#ifdef BGS_ABLATE
+int g_wide_ablate = 0;       // timing-only ablation mode (tools/wide_ablate.py)
+#endif
 int g_wide_flags = 0;        // WideArgs::flags (A/B: bits 16.. of the tuning hook's mode)
 
 }  // namespace
@@ -556,7 +558,9 @@ size_t bgs_internal_conv1x1_bfx_wide_workspace(long long M, int Cout, int K) {
 
 // tuning / test hook: mode 0 off | 1 auto | 2 every eligible layer; nst 0 auto | 2 | 3; splitk -1 auto | 1..16
 extern "C" void bgs_conv_bfx_wide_tuning(int mode, int nst, int splitk) {
-  g_wide_ablate = (mode >> 8) & 0xff;          // timing-only ablation modes (-DBGS_ABLATE builds)
+#ifdef BGS_ABLATE
+  g_wide_ablate = (mode >> 8) & 0xff;          // timing-only ablation modes; bits 8..15 are ignored in every other build
+#endif
   g_wide_flags = (mode >> 16) & 0xff;          // WideArgs::flags
   mode &= 0xff;
   g_wide_mode = mode;

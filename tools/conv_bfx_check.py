@@ -183,7 +183,7 @@ def sweep(quick):
         BF.conv_bfx_tuning()
         if R == 3 and stride == 1 and Cin % 16 == 0:
             os.environ['BGS_CONV_HALO'] = '1'
-            for hv, hs in ([(2, -1)] if quick else [(1, -1), (2, -1), (2, 1), (2, 2), (2, 4), (2, 8)]):
+            for hv, hs in ([(2, -1)] if quick else [(2, -1), (2, 1), (2, 2), (2, 4), (2, 8)]):
                 BF.conv_bfx_tuning(halo_splits=hs, halo_variant=hv)
                 res['halo%d/%d' % (hv, hs)] = run('bf16x6', lambda: bench(
                     lambda: BF.conv2d_nhwc(x, w, b, stride=1, pad=1, relu=True)))

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Timing-only ablations of the planes-in-LDS 1x1 kernel (csrc/conv1x1_planes.hip, template ABL; results are WRONG in every
 arm but 0): where does the launch spend its time beyond the MFMAs?  One child process per arm (the arm is latched from
-BGS_BFX_PLANES_ABLATE at the first launch): python tools/planes_ablate.py [N H W Cin Cout [res_mode]]   (default fpn.lat0)
+BGS_BFX_PLANES_ABLATE at the first launch).  Needs the `ablate` build of the library:
+    python -m balancedgroupsoftmax_amd.csrc.build --variant ablate
+    BGS_LIB_VARIANT=ablate python tools/planes_ablate.py [N H W Cin Cout [res_mode]]   (default fpn.lat0)
 arms: 0 full | 1 filter fragments loaded once | 2 activation tile loaded once | 3 = 1 + 2 | 4 no output stores |
 7 = no operand loads, no stores (MFMAs + LDS + skeleton) | 8 no MFMAs | 12 no MFMAs, no stores | 15 skeleton only"""
 import os
@@ -46,6 +48,11 @@ def child(shape):
 
 
 def main():
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from balancedgroupsoftmax_amd import capi
+    if os.path.basename(capi.lib_path()) != 'libbgs_ablate.so':
+        sys.exit('tools/planes_ablate.py times kernels that exist only in the `ablate` build of the library (loaded: %s):\n'
+             '    python -m balancedgroupsoftmax_amd.csrc.build --variant ablate; BGS_LIB_VARIANT=ablate python tools/planes_ablate.py' % capi.lib_path())
     if len(sys.argv) > 1 and sys.argv[1] == '--child':
         child([int(v) for v in sys.argv[2:8]])
         return

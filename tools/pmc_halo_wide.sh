@@ -1,17 +1,27 @@
 #!/bin/bash
 # SQ / GRBM counters of the halo 3x3 kernels on the two-round map: variant 4, variant 7, and variant 7's timing-only
 # ablations (no filter DMA / nothing but MFMAs).  GRBM_GUI_ACTIVE / duration = the clock the chip sustains.
+# The ablations exist only in the `ablate` build of the library:
+#   python -m balancedgroupsoftmax_amd.csrc.build --variant ablate; BGS_LIB_VARIANT=ablate bash tools/pmc_halo_wide.sh [tag]
 set -u
 TAG=${1:-pmc_halo_wide}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
+# the library that would be loaded (BGS_LIB_PATH / BGS_LIB_VARIANT), the test of tools/halo_wide_once.py
+LIB=$(cd $R && python -c "from balancedgroupsoftmax_amd import capi; print(capi.lib_path())")
+if [ "$(basename "$LIB")" != libbgs_ablate.so ]; then
+  echo "tools/pmc_halo_wide.sh needs the ablate build of the library (would load: $LIB): BGS_LIB_VARIANT=ablate bash tools/pmc_halo_wide.sh" >&2
+  exit 2
+fi
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
 for ARM in "0 0" "1 0" "1 4" "1 7"; do
   set -- $ARM
   D=$OUT/w$1_a$2
   timeout -k 3 200 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA --output-format csv -d $D -o k -- python $R/tools/halo_wide_once.py $1 $2 > $D.log 2> $D.err
-  echo "arm $ARM rc=$?"
+  rc=$?
+  echo "arm $ARM rc=$rc"
+  [ $rc -eq 0 ] || exit $rc      # nothing more is started on the GPU after a failed arm
 done
 python - <<PY
 import csv, glob, collections
