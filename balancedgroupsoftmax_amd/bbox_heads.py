@@ -70,6 +70,11 @@ class BBoxHead(nn.Module):
     def num_reg_outputs(self):
         return 4 * self.num_reg_classes
 
+    def _reg_slots(self, bbox_pred):
+        """Regression slots per row of ``bbox_pred``: 1 for a 4-column prediction (class-agnostic, or already gathered to
+        each RoI's own class by ``forward(reg_labels=...)``), else ``num_reg_classes``."""
+        return 1 if bbox_pred.shape[1] == 4 else self.num_reg_classes
+
     def init_weights(self):
         # bbox_head.py:63-69
         if self.with_cls:
@@ -117,7 +122,7 @@ class BBoxHead(nn.Module):
         if type(lb).__name__ != 'SmoothL1Loss':
             raise NotImplementedError('HIP box loss implements SmoothL1Loss only')
         val = BF.bbox_smooth_l1_loss(bbox_pred, labels, bbox_targets, bbox_weights,
-                                     self.num_reg_classes, beta=lb.beta,
+                                     self._reg_slots(bbox_pred), beta=lb.beta,
                                      avg_factor=bbox_targets.size(0), loss_weight=lb.loss_weight)
         if label_weights is not None and label_weights.is_cuda:
             if n_real is None:      # (the GS heads pass bin 0's avg factor = max(#real rows, 1))
@@ -278,10 +283,16 @@ class ConvFCBBoxHead(BBoxHead):
             self._fc1_key = key
         return self._fc1_perm
 
-    def forward(self, x, nhwc=False):
+    def forward(self, x, nhwc=False, reg_labels=None):
         """``x``: RoI features ``[K, C, h, w]`` (reference layout) or, with ``nhwc=True``,
         ``[K, h, w, C]`` as produced by our RoIAlign.  Every FC runs in the MFMA GEMM kernel (bias +
-        ReLU fused).  (torch restatement for the CPU checks: oracle/tensor_forms.convfc_bbox_forward.)"""
+        ReLU fused).  (torch restatement for the CPU checks: oracle/tensor_forms.convfc_bbox_forward.)
+
+        ``reg_labels`` (training: the RoIs' target classes ``[K]`` int64): a class-specific ``fc_reg`` that no gradient
+        reaches then returns ``bbox_pred [K, 4]`` = the deltas of each RoI's own class, the only slot the box loss and the
+        cascade's refine step read (``BF.fc_reg_gather``: 4 of the 4 x num_classes dot products per RoI, one small launch on
+        the main stream, no fork).  Without it, or when ``fc_reg`` / its input needs a gradient, the dense ``[K, 4 x
+        num_classes]``."""
         BF._require_cuda(x)
         if self.with_avg_pool:
             if nhwc:
@@ -314,6 +325,11 @@ class ConvFCBBoxHead(BBoxHead):
         # fc_cls (80 workgroups x 4 K slices) and fc_reg (312) both read the last hidden activation: a frozen fc_reg
         # with no reg branch of its own runs beside fc_cls on the side stream (functional.forked)
         fk = None
+        if reg_labels is not None and self.with_reg and not self.reg_class_agnostic and BF.fc_reg_gather_enabled() and \
+                not (torch.is_grad_enabled() and (x_reg.requires_grad or self.fc_reg.weight.requires_grad or
+                                                  (self.fc_reg.bias is not None and self.fc_reg.bias.requires_grad))):
+            cls_score = fc_apply(self.fc_cls, x_cls, False, False, h_cls) if self.with_cls else None
+            return cls_score, BF.fc_reg_gather(x_reg, self.fc_reg.weight, self.fc_reg.bias, reg_labels)
         if self.with_cls and self.with_reg and not self.reg_fcs and BF.shortcut_fork_enabled() and \
                 not (torch.is_grad_enabled() and (x_reg.requires_grad or self.fc_reg.weight.requires_grad)):
             with BF.forked(x_reg.device) as fk:
@@ -491,7 +507,7 @@ class GSBBoxHeadWith0(SharedFCBBoxHead):
                 bin_loss_weight=[w * loss_scale for w in self._bin_loss_weight_host]
                 if loss_scale != 1.0 else self._bin_loss_weight_host,
                 bbox_pred=bbox_pred, bbox_targets=bbox_targets, bbox_weights=bbox_weights,
-                num_reg_classes=self.num_reg_classes,
+                num_reg_classes=self._reg_slots(bbox_pred) if bbox_pred is not None else self.num_reg_classes,
                 beta=self.loss_bbox.beta if bbox_pred is not None else 1.0,
                 box_loss_weight=(self.loss_bbox.loss_weight if bbox_pred is not None else 1.0) * loss_scale)
             parts = BF.unbind_terms(terms)   # ONE autograd node for all terms; unit gradients pass by identity

@@ -69,6 +69,8 @@ SIGNATURES = {
     'bgs_bbox_smooth_l1_fwd_bwd': (ctypes.c_int, [c_f32p, c_i64p, c_f32p, c_f32p, ctypes.c_int,
                                                   ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                                   ctypes.c_float, c_f32p, c_f32p, c_ptr, c_ptr]),
+    'bgs_fc_reg_gather': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i64p, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, c_f32p, c_ptr]),
     'bgs_conv2d_nhwc_f32': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p] + [ctypes.c_int] * 11
                             + [c_ptr]),
     'bgs_conv2d_workspace_bytes': (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int]),
@@ -107,6 +109,9 @@ SIGNATURES = {
                                       + [ctypes.c_int] * 7 + [c_ptr, ctypes.c_size_t, c_ptr]),
     'bgs_conv3x3_halo_nhwc_f32_bfx_ex': (ctypes.c_int, [c_f32p, c_ptr, c_f32p, c_f32p, c_f32p]
                                          + [ctypes.c_int] * 7 + [c_ptr, ctypes.c_size_t, c_ptr]),
+    'bgs_conv3x3_planes_head_nhwc_f32_bfx': (ctypes.c_int, [c_f32p, c_ptr, c_f32p, c_ptr, c_f32p, c_f32p]
+                                             + [ctypes.c_int] * 7 + [c_ptr]),
+    'bgs_conv3x3_planes_head_eligible': (ctypes.c_int, [ctypes.c_int] * 6),
     'bgs_gs_loss_tuning': (None, [ctypes.c_int]),
     'bgs_gs_head_fold': (None, [ctypes.c_int]),
     'bgs_gs_loss_wavepriv_min_rows': (None, [ctypes.c_int]),

@@ -27,6 +27,8 @@
 // rounding).  LDS 45 KB, three workgroups per CU.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #ifndef BGS_P3_A_AUX
 #define BGS_P3_A_AUX 0
 #endif
@@ -76,8 +78,26 @@ struct Planes3Args {
 
 constexpr int kOob = 0x7f000000;   // byte offset past every descriptor this kernel builds: the load returns 0
 
-template <int NB>
-__global__ __launch_bounds__(kThreads, 3) void conv3x3_planes_bfx_kernel(Planes3Args g) {
+// HEAD form (rpn_conv -> rpn_cls + rpn_reg, mmdet/models/anchor_heads/rpn_head.py:30-35): a 1x1 conv with CH <= 32 output
+// channels on the 256-channel tile this workgroup owns, in its epilogue; only [N, H, W, CH] is stored.
+struct Planes3HeadArgs {
+  Planes3Args g;
+  const __bf16* hs;      // split head filter [3][Cout / 16][CH][16] (bgs_conv_bfx_split_weights of [CH][Cout])
+  const float* hbias;    // [CH] or null
+  float* hy;             // [N, H, W, CH]
+  int CH;
+};
+
+template <bool HEAD>
+struct Planes3ArgsOf { typedef Planes3Args type; };
+template <>
+struct Planes3ArgsOf<true> { typedef Planes3HeadArgs type; };
+__device__ __forceinline__ const Planes3Args& planes3_base(const Planes3Args& a) { return a; }
+__device__ __forceinline__ const Planes3Args& planes3_base(const Planes3HeadArgs& a) { return a.g; }
+
+template <int NB, bool HEAD = false>
+__global__ __launch_bounds__(kThreads, 3) void conv3x3_planes_bfx_kernel(typename Planes3ArgsOf<HEAD>::type ga) {
+  const Planes3Args& g = planes3_base(ga);
   const ConvArgs& p = g.c;
   constexpr int NS = 3, KCH = 2;                                    // k steps (16 channels) per 32-channel chunk
   constexpr int TW = 8, PW = 10, PS = 12, PSLOTS = PW * PS;        // 10 x 10 patch in rows of 12 slots
@@ -233,6 +253,112 @@ __global__ __launch_bounds__(kThreads, 3) void conv3x3_planes_bfx_kernel(Planes3
   const int e4 = (tid % TPR) * 4, er0 = tid / TPR;
   f32x4 bias = {0.f, 0.f, 0.f, 0.f};
   if (p.bias) bias = *reinterpret_cast<const f32x4*>(p.bias + n0 + e4);
+  if constexpr (HEAD) {
+    // ---- the 1x1 head on the tile.  The accumulators go through the same LDS scratch WITH bias and ReLU applied (the
+    //      writer lane owns one channel per 32-channel block: exactly the fp32 values the plain form stores), and the
+    //      head's reduction runs on them the way conv_igemm_bfx_dma_kernel<1, true> runs on the stored map: per
+    //      16-channel k step the lane's 8 fp32 values from the scratch row of its pixel, the same split3, the head filter
+    //      fragment of its output channel (rows >= CH: an offset past the descriptor = 0), the six plane products in the
+    //      ring kernel's order, k steps ascending from a zero accumulator, the head bias added last: BIT-IDENTICAL to the
+    //      two launches (tests/test_gpu_head_dead_work.py).
+    //      The k order makes the reduction of a 32-pixel half ONE chain of 96 dependent MFMAs.  Wave w holds channels
+    //      64 w .. 64 w + 63 = k steps 4 w .. 4 w + 3 of that chain, so the chain walks the waves: in stage s wave w runs
+    //      its four k steps of half s - w on its OWN 64 scratch columns (no other wave touches them: no barrier between
+    //      its write and its reads) and hands the 32 x 32 accumulator to wave w + 1 through LDS; the two halves follow
+    //      each other one stage apart: five stages of four k steps instead of two chains of sixteen, and every wave's
+    //      head filter fragments (12 x 16 bytes per lane) are in registers before the first stage.
+    static_assert(NB == 2, "the head form owns all 256 channels of a pixel");
+    const Planes3HeadArgs& hg = ga;
+    const int CH = hg.CH;
+    const int kch = p.Cout >> 4;                                      // k steps of the head: 16 (4 per wave)
+    float cb[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) cb[b] = p.bias ? p.bias[n0 + wave * 32 * NB + b * 32 + (lane & 31)] : 0.f;
+    const __amdgpu_buffer_rsrc_t h_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<__bf16*>(hg.hs), 0, (int)((size_t)NS * kch * CH * 32), 0x00020000);
+    const __amdgpu_buffer_rsrc_t hy_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(hg.hy, 0, (int)((size_t)p.M * CH * 4), 0x00020000);
+    const int h_lane = frow < CH ? frow * 32 + fk * 16 : kOob;        // bytes: output channel frow, k half fk
+    const int h_plane = kch * CH * 32;
+    const float hb = (hg.hbias && frow < CH) ? hg.hbias[frow] : 0.f;
+    bf16x8 hf[4][NS];                                                 // this wave's k steps 4 wave + u
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int s = 0; s < NS; ++s)
+        hf[u][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
+                                                  h_rsrc, h_lane, s * h_plane + (wave * 4 + u) * CH * 32, 0));
+    static_assert(32 * LD4 * 4 + 2 * 16 * 64 * 4 <= LDS_BYTES, "accumulator hand-off slots behind the scratch tile");
+    float* hand = scratch + 32 * LD4;                                 // [half][16][64] floats
+    const float* srow = scratch + frow * LD4 + wave * 64 + fk * 8;
+    auto stage = [&](auto half) {
+      constexpr int a = decltype(half)::value;
+      // the chain's MFMAs are dependent: beside the other workgroups' main loops (independent MFMAs, the pipe 0.8 busy) each
+      // of them would wait its turn at the pipe; at a raised priority the wave issues as soon as its operand is ready
+      __builtin_amdgcn_s_setprio(3);
+#pragma unroll
+      for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int i = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+          float v = acc[a][b][r];
+          v += cb[b];
+          if (p.relu) v = fmaxf(v, 0.f);
+          scratch[i * LD4 + wave * 32 * NB + b * 32 + (lane & 31)] = v;
+        }
+      f32x16 hacc;
+      if (wave == 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) hacc[r] = 0.f;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) hacc[r] = hand[(a * 16 + r) * 64 + lane];
+      }
+      // the wave's own LDS writes are visible to its own lanes behind a wave-scope fence
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(srow + u * 16);
+        const f32x4 v1 = *reinterpret_cast<const f32x4*>(srow + u * 16 + 4);
+        u32x2 h0, m0, l0, h1, m1, l1;
+        split3p(v0, h0, m0, l0);
+        split3p(v1, h1, m1, l1);
+        bf16x8 fa[NS];
+        fa[0] = __builtin_bit_cast(bf16x8, u32x4{h0[0], h0[1], h1[0], h1[1]});
+        fa[1] = __builtin_bit_cast(bf16x8, u32x4{m0[0], m0[1], m1[0], m1[1]});
+        fa[2] = __builtin_bit_cast(bf16x8, u32x4{l0[0], l0[1], l1[0], l1[1]});
+#pragma unroll
+        for (int tt = NS - 1; tt >= 0; --tt)
+#pragma unroll
+          for (int i = 0; i <= tt; ++i)
+            hacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], hf[u][tt - i], hacc, 0, 0, 0);
+      }
+      __builtin_amdgcn_s_setprio(0);
+      if (wave < 3) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) hand[(a * 16 + r) * 64 + lane] = hacc[r];
+      } else if (frow < CH) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int i = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+          const int m = a * 32 + i;
+          const int ho = ty * 8 + (m >> 3), wo = tx * TW + (m & 7);
+          if (ho < p.H && wo < p.W)
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hacc[r] + hb), hy_rsrc,
+                                                  (((n * p.H + ho) * p.W + wo) * CH + frow) * 4, 0, 0);
+        }
+      }
+    };
+#pragma unroll
+    for (int s = 0; s < 5; ++s) {
+      if (s - wave == 0) stage(std::integral_constant<int, 0>{});    // wave-uniform
+      else if (s - wave == 1) stage(std::integral_constant<int, 1>{});
+      if (s < 4) __syncthreads();                                     // the hand-off written in stage s is read in stage s + 1
+    }
+    return;
+  }
   const __amdgpu_buffer_rsrc_t y_rsrc =
       __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)((size_t)p.M * p.Cout * 4), 0x00020000);
   // ReLU-backward mask of the data-gradient form (y = mask > 0 ? y : 0, [N,H,W,Cout] like y): prefetched per half
@@ -467,15 +593,32 @@ extern "C" void bgs_conv3x3_planes_enable(int mode) { g_planes3_mode = mode < 0 
 extern "C" int bgs_conv3x3_planes_last_launch(void) { return g_planes3_last; }
 void bgs_internal_conv3x3_planes_clear_last() { g_planes3_last = 0; }
 
-// -1: not eligible / declined (the caller goes on to the halo kernels)
-int bgs_internal_conv3x3_planes(const bgs_conv::ConvArgs& pc, const void* wsplit, int KC, hipStream_t st) {
+// the dispatch rule of the stride-1 form for an [N, H, W] map with Cout channels: 0 = the kernel declines (the caller
+// goes on to the halo kernels), else the channels per workgroup / 128 (1 | 2)
+static int planes3_rule(int N, int H, int W, int Cout) {
   int mode = g_planes3_mode;                // the hook's value, else the environment (read at every call: tools/step_ab.py)
   if (mode < 0) {
     const char* e = getenv("BGS_BFX_PLANES3");
     mode = e ? atoi(e) : 1;
     if (mode < 0 || mode > 2) mode = 1;
   }
-  if (mode == 0) return -1;
+  if (mode == 0) return 0;
+  const int tiles_y = (H + 7) / 8, tiles_x = (W + 7) / 8;
+  const long long tiles_px = (long long)N * tiles_y * tiles_x;
+  static int nb_env = -1;
+  if (nb_env < 0) {
+    const char* e = getenv("BGS_BFX_PLANES3_NB");
+    nb_env = e ? atoi(e) : 0;
+  }
+  int nb = (Cout & 255) ? 1 : 2;
+  if (nb == 2 && (nb_env == 1 || (nb_env == 0 && tiles_px * (Cout / 256) <= 768))) nb = 1;
+  const long long wgs = tiles_px * (Cout / (128 * nb));
+  if (mode == 1 && wgs < 256) return 0;     // (see bgs_internal_conv3x3_planes)
+  return nb;
+}
+
+// -1: not eligible / declined (the caller goes on to the halo kernels)
+int bgs_internal_conv3x3_planes(const bgs_conv::ConvArgs& pc, const void* wsplit, int KC, hipStream_t st) {
   const ConvArgs& p = pc;
   if (p.R != 3 || p.S != 3 || p.stride != 1 || p.pad != 1 || p.rowmap || p.res_mode != 0) return -1;
   if ((p.Cin & 31) || (p.Cout & 127) || KC != 9 * (p.Cin / 16)) return -1;
@@ -484,20 +627,14 @@ int bgs_internal_conv3x3_planes(const bgs_conv::ConvArgs& pc, const void* wsplit
   if ((long long)p.N * p.H * p.W * p.Cin * 4 >= lim || (long long)p.M * p.Cout * 4 >= lim || (long long)3 * KC * p.Cout * 32 >= lim) return -1;
   const int tiles_y = (p.H + 7) / 8, tiles_x = (p.W + 7) / 8;
   const long long tiles_px = (long long)p.N * tiles_y * tiles_x;
-  static int nb_env = -1;
-  if (nb_env < 0) {
-    const char* e = getenv("BGS_BFX_PLANES3_NB");
-    nb_env = e ? atoi(e) : 0;
-  }
-  int nb = (p.Cout & 255) ? 1 : 2;
-  if (nb == 2 && (nb_env == 1 || (nb_env == 0 && tiles_px * (p.Cout / 256) <= 768))) nb = 1;
+  const int nb = planes3_rule(p.N, p.H, p.W, p.Cout);
+  if (nb == 0) return -1;
   const long long wgs = tiles_px * (p.Cout / (128 * nb));
-  if (mode == 1) {
+  {
     // automatic: wherever this kernel's grid has a workgroup per CU (profiles/r11i_planes3_ab.txt, every 3x3 / stride-1
     // layer of a cfg[1] step, interleaved, against the default halo dispatch): P2 level 756 -> 685 us, P3 level 226 ->
     // 195, layer2 conv2 84 -> 63, layer3 conv2 80 -> 72, stride-16 level 77 -> 70.  Below that (the 25 x 42 maps: 96 - 192
     // workgroups) the sliced halo plan stays ahead: layer4 conv2 80 vs 83, stride-32 level 32 vs 37.
-    if (wgs < 256) return -1;
   }
   Planes3Args g;
   g.c = p;
@@ -514,6 +651,61 @@ int bgs_internal_conv3x3_planes(const bgs_conv::ConvArgs& pc, const void* wsplit
   else hipLaunchKernelGGL((conv3x3_planes_bfx_kernel<1>), grid, block, 0, st, g);
   g_planes3_last = nb;
   bgs_internal_census_bump(BGS_CENSUS_PLANES_3X3);
+  return hipGetLastError() == hipSuccess ? BGS_OK : BGS_ERR_LAUNCH;
+}
+
+// ---- rpn_conv + the 1x1 RPN heads in one launch (the HEAD form of conv3x3_planes_bfx_kernel<2>)
+int bgs_internal_halo_hooks_default();                                   // conv_bfx.hip: no forced slice count / variant / pixel tile
+int bgs_internal_bfx_unsliced(long long M, int Cout, int KC);           // conv_bfx.hip: the operand ring would run this layer with ONE K slice
+
+// 1 when the default dispatch puts the 3x3 conv of this map on the 256-channel planes kernel AND would run the 1x1 head
+// [Chead][Cout] on it with one K slice (the arithmetic the fused epilogue reproduces bit for bit); pure host logic
+extern "C" int bgs_conv3x3_planes_head_eligible(int N, int H, int W, int Cin, int Cout, int Chead) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cout != 256 || Cin <= 0 || (Cin & 31) || Chead <= 0 || Chead > 32) return 0;
+  if (!bgs_internal_halo_hooks_default()) return 0;
+  if (planes3_rule(N, H, W, Cout) != 2) return 0;
+  return bgs_internal_bfx_unsliced((long long)N * H * W, Chead, Cout / 16) ? 1 : 0;
+}
+
+// y [N,H,W,Chead] = conv1x1(act(conv3x3(x, w) + bias), hw) + hbias; wsplit / hsplit = bgs_conv_bfx_split_weights of
+// [Cout][9 Cin] / [Chead][Cout].  Runs on every supported shape (Cout = 256, Cin % 32 == 0, Chead <= 32, 16-byte aligned
+// tensors below 2 GB), whatever bgs_conv3x3_planes_head_eligible says: the caller decides.
+extern "C" int bgs_conv3x3_planes_head_nhwc_f32_bfx(const float* x, const void* wsplit, const float* bias,
+                                                    const void* hsplit, const float* hbias, float* y, int N, int H,
+                                                    int W, int Cin, int Cout, int relu, int Chead,
+                                                    bgs_stream_t stream) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Chead <= 0) return BGS_ERR_INVALID_ARG;
+  if (!x || !wsplit || !hsplit || !y) return BGS_ERR_INVALID_ARG;
+  if (Cout != 256 || (Cin & 31) || Chead > 32) return BGS_ERR_UNSUPPORTED;
+  if (((uintptr_t)x | (uintptr_t)wsplit | (uintptr_t)hsplit) & 15) return BGS_ERR_UNSUPPORTED;
+  if (((uintptr_t)bias & 15) || (((uintptr_t)hbias | (uintptr_t)y) & 3)) return BGS_ERR_UNSUPPORTED;
+  const long long M = (long long)N * H * W, lim = kOob;
+  const int KC = 9 * (Cin / 16);
+  if (M * Cin * 4 >= lim || M * Chead * 4 >= lim || (long long)3 * KC * Cout * 32 >= lim) return BGS_ERR_UNSUPPORTED;
+  Planes3HeadArgs a;
+  Planes3Args& g = a.g;
+  ConvArgs& p = g.c;
+  p = ConvArgs();
+  p.x = x; p.w = nullptr; p.bias = bias; p.res = nullptr; p.mask = nullptr; p.y = nullptr;
+  p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.R = 3; p.S = 3; p.stride = 1; p.pad = 1;
+  p.Ho = H; p.Wo = W; p.M = (int)M; p.K = 9 * Cin; p.relu = relu; p.res_mode = 0;
+  p.partial = nullptr; p.kt_per_split = 0;
+  g.ws = reinterpret_cast<const __bf16*>(wsplit);
+  g.KC = KC;
+  g.tiles_y = (H + 7) / 8;
+  g.tiles_x = (W + 7) / 8;
+  p.tiles_m = N * g.tiles_y * g.tiles_x;
+  p.tiles_n = 1;
+  p.chunk = (p.tiles_m + 7) / 8;
+  a.hs = reinterpret_cast<const __bf16*>(hsplit);
+  a.hbias = hbias;
+  a.hy = y;
+  a.CH = Chead;
+  hipLaunchKernelGGL((conv3x3_planes_bfx_kernel<2, true>), dim3((unsigned)(8 * p.chunk)), dim3(kThreads), 0,
+                     (hipStream_t)stream, a);
+  g_planes3_last = 2;
+  bgs_internal_census_bump(BGS_CENSUS_PLANES_3X3);
+  bgs_internal_census_bump(BGS_CENSUS_PLANES_3X3_HEAD);
   return hipGetLastError() == hipSuccess ? BGS_OK : BGS_ERR_LAUNCH;
 }
 

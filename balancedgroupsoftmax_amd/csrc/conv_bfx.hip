@@ -2396,6 +2396,17 @@ inline int bfx_kc(int K) { return 2 * ((K + 31) / 32); }
 
 }  // namespace
 
+// for conv3x3_planes.hip (the fused RPN head): is the halo tuning hook at its defaults, and would the operand ring run a
+// layer with one K slice
+int bgs_internal_halo_hooks_default() {
+  return g_halo_force_splits < 0 && g_halo_variant == 4 && g_halo_geom < 0 && !g_ablate;
+}
+int bgs_internal_bfx_unsliced(long long M, int Cout, int KC) {
+  int tile, bk, want;
+  bfx_plan(M, Cout, KC, tile, bk, want);
+  return want == 1 && bfx_knobs().dma;
+}
+
 extern "C" size_t bgs_conv_bfx_weight_bytes(int rows, int K) {
   if (rows <= 0 || K <= 0) return 0;
   // three bf16 planes [3][KC][rows][16]; in the FB32 experiment (BGS_HALO_FB32=1 at process start, default off) the

@@ -248,7 +248,7 @@ class TwoStageDetector(nn.Module):
                     mask_losses = self._mask_forward_train(x, rois, targets[0], gt_masks, img.size(0))
                 mask_fk.hold(x, rois, targets, gt_masks)
             bbox_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
-            cls_score, bbox_pred = self.bbox_head(bbox_feats, nhwc=True)
+            cls_score, bbox_pred = self.bbox_head(bbox_feats, nhwc=True, reg_labels=targets[0])
             losses.update(self.bbox_head.loss(cls_score, bbox_pred, *targets))
             if mask_fk is not None:
                 mask_fk.join()
@@ -572,7 +572,7 @@ class CascadeRCNN(TwoStageDetector):
             rois, targets = self._sample_rois_fused(proposal_list, gt_bboxes, gt_labels, samplers,
                                                     rc=rc, head=head)
             feats = ext(x[:ext.num_inputs], rois)
-            cls_score, bbox_pred = head(feats, nhwc=True)
+            cls_score, bbox_pred = head(feats, nhwc=True, reg_labels=targets[0])
             if getattr(head, 'fused_loss_scale', False):      # GS heads: the stage weight rides in the kernel
                 for name, value in head.loss(cls_score, bbox_pred, *targets, loss_scale=lw).items():
                     losses['s{}.{}'.format(i, name)] = value
@@ -769,7 +769,7 @@ class HybridTaskCascade(CascadeRCNN):
             rois, targets = self._sample_rois_fused(proposal_list, gt_bboxes, gt_labels, samplers,
                                                     rc=rc, head=head)
             feats = self._fused_roi_feats(ext, x, rois, semantic_feat, 'bbox')
-            cls_score, bbox_pred = head(feats, nhwc=True)
+            cls_score, bbox_pred = head(feats, nhwc=True, reg_labels=targets[0])
             if getattr(head, 'fused_loss_scale', False):      # GS heads: the stage weight rides in the kernel
                 for name, value in head.loss(cls_score, bbox_pred, *targets, loss_scale=lw).items():
                     losses['s{}.{}'.format(i, name)] = value

@@ -595,6 +595,30 @@ def bbox_smooth_l1_loss(bbox_pred, labels, bbox_targets, bbox_weights, num_reg_c
                                loss_weight)
 
 
+def fc_reg_gather_enabled():
+    """A frozen class-specific ``fc_reg`` computes only the four columns of each RoI's own class
+    (``ConvFCBBoxHead.forward(reg_labels=...)``): ``BGS_FC_REG_GATHER=0`` (read per call) keeps the dense launch."""
+    return os.environ.get('BGS_FC_REG_GATHER', '1') != '0'
+
+
+def fc_reg_gather(x, weight, bias, labels):
+    """``y[r, 0:4] = x[r] . weight[4 l : 4 l + 4].T + bias[4 l : 4 l + 4]`` with ``l = labels[r]`` (zeros for a label
+    outside ``[0, weight.shape[0] / 4)``): the slot of the dense ``fc_reg`` output that the box loss and
+    ``refine_boxes`` read, without the other columns.  No autograd: for a frozen ``fc_reg`` only."""
+    _require_cuda(x, weight, bias, labels)
+    lib = capi.load()
+    assert x.dim() == 2 and weight.dim() == 2 and weight.shape[1] == x.shape[1] and weight.shape[0] % 4 == 0
+    assert labels.dtype == torch.int64 and labels.numel() == x.shape[0]
+    x, w = _f32c(x), _f32c(weight)
+    b = None if bias is None else _f32c(bias)
+    K, C = x.shape
+    y = torch.empty((K, 4), dtype=torch.float32, device=x.device)
+    rc = lib.bgs_fc_reg_gather(capi.ptr(x), capi.ptr(w), capi.ptr(b), capi.ptr(labels.contiguous()), K, C,
+                               w.shape[0] // 4, capi.ptr(y), capi.current_stream(x.device))
+    capi.check('bgs_fc_reg_gather', rc)
+    return y
+
+
 # ----------------------------------------------------------------------------------------
 # conv / linear on the matrix cores (NHWC fp32 activations, [Cout,R,S,Cin] fp32 weights)
 #   math 'bf16x6' (default): bf16 MFMA on exactly split operands, fp32-faithful (csrc/conv_bfx.hip)
@@ -819,7 +843,7 @@ def conv_bfx_last_launch():
 
 CENSUS = dict(bf16_ring8=0, grouped_lds=1, halo_bfx4=2, dma_ring64=3, gs_head_fused=4, conv1x1_bres=5,
               wgrad_bfx=6, roi_bwd_gather=7, bf16s=8, grouped_bf16s=9, bfx_wide=10, gs_scale_grad=11, halo_wide=12, stem_fused=13, fused_c3=14,
-              planes_3x3=15, planes_1x1=16)
+              planes_3x3=15, planes_1x1=16, planes_3x3_head=17)
 
 
 def launch_census(reset=False):
@@ -915,6 +939,44 @@ def conv3x3_c3_fused_nhwc(x, w2_krsc, bias2, w3_krsc, bias3, residual=None, relu
                                                capi.ptr(bias3), capi.ptr(residual), capi.ptr(out), N, H, W, Cmid,
                                                Cout3, int(bool(relu3)), capi.current_stream(x.device))
     capi.check('bgs_conv3x3_c3_fused_nhwc_f32_bfx', rc)
+    return out
+
+
+def rpn_head_fusion_eligible(x, w_conv, w_head):
+    """May ``conv1x1(relu(conv3x3(x, w_conv)), w_head)`` run as ONE launch (:func:`conv3x3_head_fused_nhwc`) in place of
+    the two it is bit-identical to?  Nothing may need a gradient (the 256-channel map is never stored), the arithmetic is
+    ``bf16x6`` on fp32 activations, and the default dispatch puts this map on the 256-channel 3x3 planes kernel with the
+    head unsliced (``bgs_conv3x3_planes_head_eligible``).  ``BGS_RPN_HEAD_FUSION=0`` (read per call): the two launches."""
+    if os.environ.get('BGS_RPN_HEAD_FUSION', '1') == '0' or _CONV_MATH[0] != 'bf16x6':
+        return False
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or w_conv.dim() != 4 or w_head.dim() != 4:
+        return False
+    N, H, W, Cin = x.shape
+    if tuple(w_conv.shape[1:]) != (3, 3, Cin) or tuple(w_head.shape[1:]) != (1, 1, w_conv.shape[0]):
+        return False
+    if not _use_halo_bfx(N * H * W, w_conv.shape[0]):
+        return False
+    return bool(capi.load().bgs_conv3x3_planes_head_eligible(N, H, W, Cin, w_conv.shape[0], w_head.shape[0]))
+
+
+def conv3x3_head_fused_nhwc(x, w_krsc, bias, hw_krsc, hbias, relu=True):
+    """``y [N,H,W,Chead] = conv1x1(act(conv3x3(x, w) + bias), hw) + hbias`` in ONE launch
+    (``bgs_conv3x3_planes_head_nhwc_f32_bfx``: ``rpn_conv`` with ``rpn_cls + rpn_reg`` in its epilogue); bit-identical to
+    the two ``conv2d_nhwc`` calls on the maps :func:`rpn_head_fusion_eligible` accepts.  Forward only, frozen filters."""
+    _require_cuda(x, w_krsc, bias, hw_krsc, hbias)
+    lib = capi.load()
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
+    N, H, W, Cin = x.shape
+    Cout, Ch = w_krsc.shape[0], hw_krsc.shape[0]
+    assert tuple(w_krsc.shape) == (Cout, 3, 3, Cin) and tuple(hw_krsc.shape) == (Ch, 1, 1, Cout)
+    assert w_krsc.is_contiguous() and hw_krsc.is_contiguous()
+    ws = bfx_split_weights(w_krsc.view(Cout, 9 * Cin), cache=True)
+    hs = bfx_split_weights(hw_krsc.view(Ch, Cout), cache=True)
+    out = torch.empty((N, H, W, Ch), dtype=torch.float32, device=x.device)
+    rc = lib.bgs_conv3x3_planes_head_nhwc_f32_bfx(capi.ptr(x), capi.ptr(ws), capi.ptr(bias), capi.ptr(hs),
+                                                  capi.ptr(hbias), capi.ptr(out), N, H, W, Cin, Cout,
+                                                  int(bool(relu)), Ch, capi.current_stream(x.device))
+    capi.check('bgs_conv3x3_planes_head_nhwc_f32_bfx', rc)
     return out
 
 

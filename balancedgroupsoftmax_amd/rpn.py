@@ -143,6 +143,12 @@ class RPNHead(nn.Module):
         na = self.num_anchors * self.cls_out_channels
 
         def level(x):
+            # nothing needs a gradient (frozen-RPN training, inference): the 256-channel map has no reader but the 1x1
+            # heads — on the levels of the 256-channel planes kernel (the P2 level) they run in its epilogue, ONE launch
+            ts = (x,) + tuple(f['conv']) + tuple(f['head'])
+            if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)) and \
+                    BF.rpn_head_fusion_eligible(x, f['conv'][0], f['head'][0]):
+                return BF.conv3x3_head_fused_nhwc(x, f['conv'][0], f['conv'][1], f['head'][0], f['head'][1])
             h = BF.conv2d_autograd(x, f['conv'][0], f['conv'][1], pad=1, relu='consumers')
             return BF.conv2d_autograd(h, f['head'][0], f['head'][1], mask_input=True)
 

@@ -191,6 +191,18 @@ int bgs_bbox_smooth_l1_fwd_bwd(const float* bbox_pred, const int64_t* labels,
                                bgs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Class-specific box regression for the one class per RoI that its consumers read (the box loss
+ *   above and bgs_refine_boxes gather slot (r, labels[r]) of the dense fc_reg output,
+ *   convfc_bbox_head.py:163-165 + bbox_head.py:117-129 / :210-239): the gather ahead of the product.
+ *     y[r, j] = sum_c x[r, c] * w[4 * labels[r] + j, c] + bias[4 * labels[r] + j],  j = 0..3
+ *   x [K,C] float (C % 4 == 0), w [4*R, C] float, bias [4*R] float or NULL, labels [K] int64,
+ *   y [K,4] float; a label outside [0, R) gives a zero row.  fp32 FMA, fixed summation order.
+ *   Valid only while nothing needs a gradient through fc_reg (no backward exists).
+ * ---------------------------------------------------------------------------------- */
+int bgs_fc_reg_gather(const float* x, const float* w, const float* bias, const int64_t* labels,
+                      int K, int C, int R, float* y, bgs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Convolution / linear layer as an implicit GEMM on the fp32 matrix cores.
  * Replaces what the reference delegates to cuDNN/cuBLAS via nn.Conv2d (+ eval-mode
  * BatchNorm2d folded into w/bias, + ReLU, + residual add) and nn.Linear:
@@ -357,6 +369,19 @@ int bgs_conv3x3_c3_fused_nhwc_f32_bfx(const float* x, const void* w2split, const
                                       const void* w3split, const float* bias3, const float* residual,
                                       float* y, int N, int H, int W, int Cmid, int Cout3, int relu3,
                                       bgs_stream_t stream);
+/* The RPN head of a level in ONE launch (mmdet/models/anchor_heads/rpn_head.py:30-35): rpn_conv (3x3 / stride 1 /
+ * pad 1, Cin -> 256, bias, ReLU when relu != 0) with rpn_cls + rpn_reg (one 1x1 filter [Chead][256], Chead <= 32) in its
+ * epilogue — the HEAD form of the 8 x 8-pixel planes kernel (csrc/conv3x3_planes.hip), whose workgroups own all 256
+ * channels of their pixels.  x [N,H,W,Cin] fp32 NHWC; wsplit / hsplit = bgs_conv_bfx_split_weights of [256][9 Cin] /
+ * [Chead][256]; y [N,H,W,Chead].  The 256-channel map never reaches HBM: forward only, for the case in which nothing
+ * else reads it (no gradient through the RPN).  BIT-IDENTICAL to bgs_conv3x3_halo_nhwc_f32_bfx on the planes kernel
+ * followed by bgs_conv2d_nhwc_f32_bfx_ws with one K slice.  BGS_ERR_UNSUPPORTED for other shapes.
+ * bgs_conv3x3_planes_head_eligible: 1 when the default dispatch would run exactly those two launches on this map (the
+ * 256-channel planes kernel by its own rule, the tuning hooks at their defaults, the head unsliced); host logic only. */
+int bgs_conv3x3_planes_head_nhwc_f32_bfx(const float* x, const void* wsplit, const float* bias,
+                                         const void* hsplit, const float* hbias, float* y, int N, int H,
+                                         int W, int Cin, int Cout, int relu, int Chead, bgs_stream_t stream);
+int bgs_conv3x3_planes_head_eligible(int N, int H, int W, int Cin, int Cout, int Chead);
 
 
 /* Grouped 3x3 convolution (pad 1, stride 1 or 2) + bias + ReLU, NHWC: conv2 of the ResNeXt
