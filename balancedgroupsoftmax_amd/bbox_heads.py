@@ -174,6 +174,46 @@ class BBoxHead(nn.Module):
         from .post_processing import multiclass_nms
         return multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
 
+    @force_fp32(apply_to=('cls_score', 'bbox_pred'))
+    def get_det_bboxes_batched(self, rois, cls_score, bbox_pred, img_shapes, scale_factors, rescale=False):
+        """:meth:`get_det_bboxes` (``cfg=None``) for the ``B`` images of a batch at once: ``rois [B*n, 5]`` (image
+        ``b``'s ``n`` rows together, in image order), ``img_shapes`` / ``scale_factors``: one per image (float
+        scales) -> ``(bboxes [B,n,4C] or [B,n,4], scores [B,n,C])``.  The same tensor operations with per-row clamp
+        bounds and a per-row scale, so image ``b``'s rows are bit-identical to the per-image call on its rows."""
+        from .box_ops import clamp_boxes_rows, delta2bbox, rows_of
+        B = len(img_shapes)
+        assert B >= 1 and rois.size(0) % B == 0 and len(scale_factors) == B
+        n = rois.size(0) // B
+        if isinstance(cls_score, list):
+            cls_score = sum(cls_score) / float(len(cls_score))
+        scores = self._scores(cls_score)
+        if bbox_pred is not None:
+            bboxes = delta2bbox(rois[:, 1:], bbox_pred, self.target_means, self.target_stds, None)
+        else:
+            bboxes = rois[:, 1:].clone()
+        bboxes = clamp_boxes_rows(bboxes, rows_of([s[1] - 1 for s in img_shapes], n, bboxes),
+                                  rows_of([s[0] - 1 for s in img_shapes], n, bboxes))
+        if rescale:
+            # `bboxes / python_float` multiplies by the float32 reciprocal of the scalar on the device; the per-row
+            # form does the same with each image's own reciprocal
+            inv = [float(np.float32(1.0) / np.float32(s)) for s in scale_factors]
+            bboxes = bboxes * rows_of(inv, n, bboxes)
+        return bboxes.view(B, n, -1), (scores.view(B, n, -1) if scores is not None else None)
+
+    @force_fp32(apply_to=('bbox_pred', ))
+    def regress_by_class_batched(self, rois, label, bbox_pred, wmax, hmax):
+        """:meth:`regress_by_class` for ``[B*n, 5]`` rois of several images: the same tensor operations with the
+        per-row clamp bounds ``wmax`` / ``hmax`` ``[B*n, 1]`` (``img_shape[1] - 1`` / ``img_shape[0] - 1``)."""
+        from .box_ops import clamp_boxes_rows, delta2bbox
+        assert rois.size(1) == 5
+        if not self.reg_class_agnostic:
+            cols = (label * 4).view(-1, 1) + torch.arange(4, device=label.device).view(1, 4)
+            bbox_pred = torch.gather(bbox_pred, 1, cols)
+        assert bbox_pred.size(1) == 4
+        boxes = clamp_boxes_rows(delta2bbox(rois[:, 1:], bbox_pred, self.target_means, self.target_stds, None),
+                                 wmax, hmax)
+        return torch.cat((rois[:, [0]], boxes), dim=1)
+
     @force_fp32(apply_to=('bbox_preds', ))
     def refine_bboxes(self, rois, labels, bbox_preds, pos_is_gts, img_metas):
         """Cascade stage hand-over (bbox_head.py:169-208): regress every RoI with its own

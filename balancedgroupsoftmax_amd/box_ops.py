@@ -58,6 +58,27 @@ def delta2bbox(rois, deltas, means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.), max_
     return torch.stack([x1, y1, x2, y2], dim=-1).view(n, k4)
 
 
+def rows_of(values, n, like):
+    """One python number per image -> ``[len(values) * n, 1]`` tensor (image ``b``'s value in its ``n`` rows), built
+    on the device with fills: no host-to-device copy, no synchronisation."""
+    return torch.stack([like.new_full((n,), float(v)) for v in values]).view(len(values) * n, 1)
+
+
+def clamp_boxes_rows(boxes, wmax, hmax):
+    """``delta2bbox``'s ``max_shape`` clamp with per-row bounds: boxes ``[N, 4k]``, ``wmax`` / ``hmax`` ``[N, 1]``
+    (``img_shape[1] - 1`` / ``img_shape[0] - 1`` of the row's image).  ``clamp(min=0, max=m)`` is
+    ``min(max(x, 0), m)``; this is the same pair of operations with a tensor bound, so the values are bit-identical
+    to ``delta2bbox(..., max_shape)`` on the rows of one image."""
+    N, k4 = boxes.shape
+    b = boxes.view(N, k4 // 4, 4)
+    w, h = wmax.view(N, 1), hmax.view(N, 1)
+    x1 = torch.minimum(b[..., 0].clamp(min=0), w)
+    y1 = torch.minimum(b[..., 1].clamp(min=0), h)
+    x2 = torch.minimum(b[..., 2].clamp(min=0), w)
+    y2 = torch.minimum(b[..., 3].clamp(min=0), h)
+    return torch.stack([x1, y1, x2, y2], dim=-1).view(N, k4)
+
+
 def bbox2roi(bbox_list):
     """list of per-image ``[n_i, >=4]`` boxes -> ``[sum n_i, 5]`` (batch_ind, x1, y1, x2, y2)."""
     parts = []

@@ -204,6 +204,10 @@ SIGNATURES = {
     'bgs_nms_gather': (ctypes.c_int, [c_f32p, c_ptr, c_ptr, ctypes.c_int, ctypes.c_int, c_f32p, c_f32p, c_ptr]),
     'bgs_soft_nms_batched': (ctypes.c_int, [c_f32p, c_ptr, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                             ctypes.c_float, ctypes.c_float, c_ptr, c_f32p, c_ptr, c_ptr]),
+    'bgs_det_candidates': (ctypes.c_int, [c_f32p, c_f32p, c_ptr, c_f32p] + [ctypes.c_int] * 4
+                           + [ctypes.c_float, ctypes.c_int, c_f32p, c_ptr, c_ptr, c_ptr]),
+    'bgs_det_select': (ctypes.c_int, [c_f32p, c_ptr, c_ptr, c_f32p, c_ptr] + [ctypes.c_int] * 4
+                       + [c_f32p, c_ptr, c_ptr, c_ptr, c_ptr]),
     'bgs_gather_boxes': (ctypes.c_int, [c_f32p, c_ptr, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p,
                                         c_ptr, c_ptr]),
     'bgs_aug_map_boxes': (ctypes.c_int, [c_ptr, c_ptr] + [ctypes.c_int] * 4 + [c_ptr, c_ptr, c_ptr, ctypes.c_int,

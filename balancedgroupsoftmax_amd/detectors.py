@@ -347,6 +347,84 @@ class TwoStageDetector(nn.Module):
                                             img_meta[0]['ori_shape'], img_meta[0]['scale_factor'], rescale,
                                             encode=encode)
 
+    # ------------------------------------------------------------------ batched test: several images per pass
+    def _check_batch(self, img, img_metas):
+        """The limits of simple_test_batch, raised before any device work."""
+        B = int(img.size(0))
+        if len(img_metas) != B:
+            raise ValueError('simple_test_batch: {} images but {} image metas'.format(B, len(img_metas)))
+        if self.with_rpn:
+            L = len(self.rpn_head.anchor_strides)
+            if B * L > 64:
+                raise NotImplementedError(
+                    'simple_test_batch: images x pyramid levels <= 64 (the row limit of bgs_topk_sorted_f32: %d images '
+                    'with %d levels); got %d images' % (64 // L, L, B))
+        for m in img_metas:
+            if m.get('flip', False):
+                raise NotImplementedError('simple_test_batch: flip=True is aug_test ground (one image per call)')
+            if not isinstance(m['scale_factor'], float):
+                raise NotImplementedError('simple_test_batch: scale_factor must be a float (keep_ratio=True); the '
+                                          'array form is not built (got %r)' % (m['scale_factor'],))
+
+    def _batch_rois(self, x, img_metas, proposals):
+        """The fixed-shape proposals of the batch (the RPN's, or the caller's ``ProposalList`` / list of
+        ``(props, valid)``) -> ``rois [B*n, 5]`` with the image index in column 0, ``valid [B, n]`` or ``None``."""
+        from .box_ops import rows_of
+        if proposals is None:
+            proposals = self.simple_test_rpn(x, img_metas, self.test_cfg.rpn)
+        if hasattr(proposals, 'batched'):
+            props, valid = proposals.batched
+        elif isinstance(proposals[0], tuple):
+            props, valid = torch.stack([p for p, _ in proposals]), torch.stack([v for _, v in proposals])
+        else:
+            props, valid = torch.stack(list(proposals)), None
+        B, n = props.shape[:2]
+        rois = torch.cat([rows_of(range(B), n, props).view(B, n, 1), props[..., :4]], dim=2).view(B * n, 5)
+        return rois, valid
+
+    def _batch_det_rows(self, dets, labels, counts, img_metas, rescale):
+        """The ONE size read of a batch with a mask branch: the real detections of all images concatenated ->
+        ``(mask_rois [K, 5], labels [K], sizes)``; the mask boxes are in the network input's scale."""
+        sizes = counts.cpu().tolist()
+        rois, labs = [], []
+        for b, k in enumerate(sizes):
+            boxes = dets[b, :k, :4] * img_metas[b]['scale_factor'] if rescale else dets[b, :k, :4]
+            rois.append(torch.cat([boxes.new_full((k, 1), float(b)), boxes], dim=1))
+            labs.append(labels[b, :k])
+        return torch.cat(rois), torch.cat(labs), sizes
+
+    def simple_test_batch(self, img, img_metas, proposals=None, rescale=False, feats=None):
+        """``simple_test`` for ``B`` images that share one padded tensor shape: ``img [B, 3, H, W]``, ``img_metas`` a
+        list of ``B`` dicts (``img_shape``, ``scale_factor`` and ``ori_shape`` per image).  Returns a list of ``B``
+        items, each what ``simple_test`` returns for that image.  One trunk / RPN / RoI head pass over the batch, the
+        box tail of all images in a fixed number of launches (``multiclass_nms_batched``), one device-to-host copy;
+        with a mask branch the mask head runs once over all images' detections after the single size read.
+        ``feats``: ``extract_feat(img)`` computed ahead (``train.TrunkPipeline(inference=True)``)."""
+        from .post_processing import bbox2result_batched, multiclass_nms_batched
+        assert self.with_bbox, 'Bbox head must be implemented.'
+        self._check_batch(img, img_metas)
+        with torch.no_grad():
+            x = self.extract_feat(img) if feats is None else feats
+            rois, valid = self._batch_rois(x, img_metas, proposals)
+            roi_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
+            cls_score, bbox_pred = self.bbox_head(roi_feats, nhwc=True)
+            bboxes, scores = self.bbox_head.get_det_bboxes_batched(
+                rois, cls_score, bbox_pred, [m['img_shape'] for m in img_metas],
+                [m['scale_factor'] for m in img_metas], rescale=rescale)
+            cfg = self.test_cfg.rcnn
+            dets, labels, counts = multiclass_nms_batched(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img,
+                                                          valid=valid)
+            if not self.with_mask:
+                return bbox2result_batched(dets, labels, counts, self.bbox_head.num_classes)
+            mask_rois, mask_labels, sizes = self._batch_det_rows(dets, labels, counts, img_metas, rescale)
+            if mask_rois.shape[0] == 0:
+                probs = mask_rois.new_zeros((0, 28, 28))
+            else:
+                mask_feats = self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], mask_rois)
+                probs = self.mask_head.get_mask_probs(self.mask_head.features(mask_feats, nhwc=True), mask_labels)
+            results = bbox2result_batched(dets, labels, counts, self.bbox_head.num_classes)
+            return list(zip(results, torch.split(probs, sizes)))
+
     # ------------------------------------------------------------------ test-time augmentation
     def extract_feats(self, imgs):
         """base.py:47-49.  aug_test computes every view's features ONCE and keeps them for the RPN, box and mask
@@ -633,6 +711,44 @@ class CascadeRCNN(TwoStageDetector):
         return self.bbox_head[-1].get_det_bboxes(rois, cls_score, bbox_pred, img_meta[0]['img_shape'],
                                                  img_meta[0]['scale_factor'], rescale=False, cfg=None)
 
+    def _bbox_roi_feats(self, ext, x, rois, semantic_feat):
+        return ext(x[:ext.num_inputs], rois)
+
+    def _batch_dets(self, x, img_metas, proposals, rescale, semantic_feat=None):
+        """The stage loop of ``simple_test`` over the ``[B*n, 5]`` rois of a batch (every stage re-regresses with its
+        arg-max class against the row's own image shape: ``regress_by_class_batched``), the stage-averaged logits,
+        ``get_det_bboxes_batched`` and the batched box tail -> ``(dets, labels, counts)`` of
+        ``multiclass_nms_batched``."""
+        from .box_ops import rows_of
+        from .post_processing import multiclass_nms_batched
+        rois, valid = self._batch_rois(x, img_metas, proposals)
+        n = rois.size(0) // len(img_metas)
+        wmax = rows_of([m['img_shape'][1] - 1 for m in img_metas], n, rois)
+        hmax = rows_of([m['img_shape'][0] - 1 for m in img_metas], n, rois)
+        ms_scores = []
+        for i in range(self.num_stages):
+            head, ext = self.bbox_head[i], self.bbox_roi_extractor[i]
+            cls_score, bbox_pred = head(self._bbox_roi_feats(ext, x, rois, semantic_feat), nhwc=True)
+            ms_scores.append(cls_score)
+            if i < self.num_stages - 1:
+                rois = head.regress_by_class_batched(rois, cls_score.argmax(dim=1), bbox_pred, wmax, hmax)
+        cls_score = sum(ms_scores) / float(self.num_stages)
+        bboxes, scores = self.bbox_head[-1].get_det_bboxes_batched(
+            rois, cls_score, bbox_pred, [m['img_shape'] for m in img_metas],
+            [m['scale_factor'] for m in img_metas], rescale=rescale)
+        cfg = self.test_cfg.rcnn
+        return multiclass_nms_batched(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img, valid=valid)
+
+    def simple_test_batch(self, img, img_metas, proposals=None, rescale=False, feats=None):
+        """``simple_test`` for ``B`` images of one padded shape (see ``TwoStageDetector.simple_test_batch``): a list
+        of ``B`` ``bbox_results``."""
+        from .post_processing import bbox2result_batched
+        self._check_batch(img, img_metas)
+        with torch.no_grad():
+            x = self.extract_feat(img) if feats is None else feats
+            dets, labels, counts = self._batch_dets(x, img_metas, proposals, rescale)
+            return bbox2result_batched(dets, labels, counts, self.bbox_head[-1].num_classes)
+
     def _aug_test_dets(self, feats, img_metas, proposals, semantic_feats):
         """cascade_rcnn.py:445-503 / htc.py:441-504: merged proposals (or the caller's, original scale) mapped into
         every view, each view's stage loop, boxes and scores merged, ``multiclass_nms``."""
@@ -840,6 +956,29 @@ class HybridTaskCascade(CascadeRCNN):
         boxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes[:, :4]
         mask_rois = torch.cat([boxes.new_zeros((boxes.size(0), 1)), boxes], dim=1)
         return det_bboxes, det_labels, self._ensemble_masks(x, mask_rois, det_labels, semantic_feat)
+
+    def _bbox_roi_feats(self, ext, x, rois, semantic_feat):
+        return self._fused_roi_feats(ext, x, rois, semantic_feat, 'bbox')
+
+    def simple_test_batch(self, img, img_metas, proposals=None, rescale=False, feats=None):
+        """``simple_test`` for ``B`` images of one padded shape (see ``TwoStageDetector.simple_test_batch``): a list
+        of ``B`` ``(bbox_results, probs [k_b, 28, 28])``.  The mask ensemble runs once over the detections of all
+        images, after the batch's single size read."""
+        from .post_processing import bbox2result_batched
+        if self.test_cfg.get('keep_all_stages', False):
+            raise NotImplementedError('keep_all_stages=True (per-stage results) is not built')
+        self._check_batch(img, img_metas)
+        with torch.no_grad():
+            x = self.extract_feat(img) if feats is None else feats
+            semantic_feat = self.semantic_head(x)[1] if self.with_semantic else None
+            dets, labels, counts = self._batch_dets(x, img_metas, proposals, rescale, semantic_feat)
+            mask_rois, mask_labels, sizes = self._batch_det_rows(dets, labels, counts, img_metas, rescale)
+            if mask_rois.shape[0] == 0:
+                probs = mask_rois.new_zeros((0, 28, 28))
+            else:
+                probs = self._ensemble_masks(x, mask_rois, mask_labels, semantic_feat)
+            results = bbox2result_batched(dets, labels, counts, self.bbox_head[-1].num_classes)
+            return list(zip(results, torch.split(probs, sizes)))
 
     def _ensemble_masks(self, x, mask_rois, det_labels, semantic_feat):
         """htc.py:379-405: every stage's mask head on the final boxes' features (mask information

@@ -1855,6 +1855,88 @@ def soft_nms_batched(dets, counts, iou_thr, method='linear', sigma=0.5, min_scor
     return order, scores, keep_count
 
 
+DET_CANDIDATE_MODES = {'sorted': 0, 'original': 1}
+DET_SELECT_WORKSPACE_PER_IMAGE = 65536
+
+
+def det_candidates(scores, boxes, score_thr, mode='sorted', valid=None, score_factors=None, out=None):
+    """The candidate lists of all ``B * (C - 1)`` (image, class) problems in ONE launch (``bgs_det_candidates``).
+    scores ``[B,n,C]`` f32 (column 0 = background), boxes ``[B,n,4C]`` or ``[B,n,4]`` f32 (decoded), valid
+    ``[B,n]`` bool / uint8, score_factors ``[B,n]`` -> ``dets [B*(C-1),n,5]``, ``idx [B*(C-1),n]`` i32 (row
+    inside the image), ``counts [B*(C-1)]`` i32.  ``mode='sorted'``: the rows with raw score ``> score_thr`` by
+    descending score x factor, ties by ascending row (hard NMS); ``'original'``: in row order (soft-NMS).  Slots
+    past the count are zero, ``idx`` -1.  ``n <= 4096``.  No host sync."""
+    _require_cuda(scores, boxes, valid, score_factors)
+    code = DET_CANDIDATE_MODES.get(mode, mode)
+    if code not in (0, 1):
+        raise ValueError('det_candidates: mode must be "sorted" or "original" (got %r)' % (mode,))
+    lib = capi.load()
+    assert scores.dim() == 3 and boxes.dim() == 3 and scores.dtype == torch.float32 and boxes.dtype == torch.float32
+    B, n, C = scores.shape
+    assert boxes.shape[:2] == (B, n) and boxes.shape[2] in (4, 4 * C) and C >= 2 and n >= 1 and B >= 1
+    scores, boxes = scores.detach().contiguous(), boxes.detach().contiguous()
+    if valid is not None:
+        assert valid.shape == (B, n) and valid.dtype in (torch.bool, torch.uint8)
+        valid = valid.contiguous().view(torch.uint8)
+    if score_factors is not None:
+        assert score_factors.shape == (B, n)
+        score_factors = _f32c(score_factors)
+    dev = scores.device
+    P = B * (C - 1)
+    if out is None:
+        out = (torch.empty((P, n, 5), dtype=torch.float32, device=dev),
+               torch.empty((P, n), dtype=torch.int32, device=dev),
+               torch.empty((P,), dtype=torch.int32, device=dev))
+    dets, idx, counts = out
+    assert dets.shape == (P, n, 5) and dets.dtype == torch.float32 and dets.is_contiguous()
+    assert idx.shape == (P, n) and idx.dtype == torch.int32 and idx.is_contiguous()
+    assert counts.shape == (P,) and counts.dtype == torch.int32
+    rc = lib.bgs_det_candidates(capi.ptr(scores), capi.ptr(boxes), capi.ptr(valid) if valid is not None else None,
+                                capi.ptr(score_factors) if score_factors is not None else None, B, n, C,
+                                int(boxes.shape[2]), float(score_thr), int(code), capi.ptr(dets), capi.ptr(idx),
+                                capi.ptr(counts), capi.current_stream(dev))
+    capi.check('bgs_det_candidates', rc)
+    return dets, idx, counts
+
+
+def det_select(dets, idx, keep, keep_count, num_imgs, max_num, sel_scores=None, out=None):
+    """The final fixed-shape detections of ``num_imgs`` images (``bgs_det_select``: two launches whatever the batch,
+    no host sync).  ``dets [P,n,5]`` / ``idx [P,n]`` of :func:`det_candidates`, ``keep`` / ``keep_count`` of
+    :func:`nms_batched`, or ``order`` / ``keep_count`` and ``sel_scores`` of :func:`soft_nms_batched`;
+    ``P = num_imgs * (C - 1)`` -> ``out_dets [B,max_num,5]``, ``out_labels [B,max_num]`` i32 (0-based, -1 in the
+    unused slots), ``out_count [B]`` i32.  Nothing cut: class-major (hard: ascending original row inside a class,
+    soft: selection order); cut: by descending score, ties in class-major concatenation order.
+    ``max_num <= min(n * (C - 1), 4096)``."""
+    _require_cuda(dets, idx, keep, keep_count, sel_scores)
+    lib = capi.load()
+    assert dets.dim() == 3 and dets.shape[2] == 5 and dets.dtype == torch.float32 and dets.is_contiguous()
+    P, n, _ = dets.shape
+    B = int(num_imgs)
+    assert B >= 1 and P % B == 0 and int(max_num) > 0
+    for t in (idx, keep):
+        assert t.shape == (P, n) and t.dtype == torch.int32 and t.is_contiguous()
+    assert keep_count.shape == (P,) and keep_count.dtype == torch.int32
+    if sel_scores is not None:
+        assert sel_scores.shape == (P, n) and sel_scores.dtype == torch.float32 and sel_scores.is_contiguous()
+    dev = dets.device
+    max_num = int(max_num)
+    if out is None:
+        out = (torch.empty((B, max_num, 5), dtype=torch.float32, device=dev),
+               torch.empty((B, max_num), dtype=torch.int32, device=dev),
+               torch.empty((B,), dtype=torch.int32, device=dev))
+    out_dets, out_labels, out_count = out
+    assert out_dets.shape == (B, max_num, 5) and out_dets.dtype == torch.float32 and out_dets.is_contiguous()
+    assert out_labels.shape == (B, max_num) and out_labels.dtype == torch.int32 and out_labels.is_contiguous()
+    assert out_count.shape == (B,) and out_count.dtype == torch.int32
+    ws = _workspace(B * DET_SELECT_WORKSPACE_PER_IMAGE, dev)
+    rc = lib.bgs_det_select(capi.ptr(dets), capi.ptr(idx), capi.ptr(keep),
+                            capi.ptr(sel_scores) if sel_scores is not None else None,
+                            capi.ptr(keep_count.contiguous()), B, P // B, n, max_num, capi.ptr(out_dets),
+                            capi.ptr(out_labels), capi.ptr(out_count), capi.ptr(ws), capi.current_stream(dev))
+    capi.check('bgs_det_select', rc)
+    return out_dets, out_labels, out_count
+
+
 def nms_gather(boxes, keep, keep_count):
     """``boxes [R,nmax,5]``, ``keep [R,nmax]`` / ``keep_count [R]`` of :func:`nms_batched` ->
     ``(kept [R,nmax,5], scores [R,nmax])``: the kept boxes in fixed-shape rows, score -1 in the slots

@@ -130,6 +130,76 @@ def _multiclass_soft_nms(multi_bboxes, multi_scores, score_thr, cfg, max_num, sc
     return rows.reshape(-1, 5)[top], labels_all.reshape(-1)[top]
 
 
+def multiclass_nms_batched(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num, score_factors=None, valid=None,
+                           iou_mode=0):
+    """:func:`multiclass_nms` for the ``B`` images of a batch in a fixed number of launches and WITHOUT a host
+    synchronisation: ``multi_bboxes [B,n,4C]`` or ``[B,n,4]``, ``multi_scores [B,n,C]``, ``score_factors`` /
+    ``valid`` ``[B,n]`` (rows with ``valid == 0`` are never candidates) ->
+    ``(dets [B,max_num,5], labels [B,max_num] int64, counts [B] int32)`` device tensors; image ``b``'s detections
+    are ``dets[b, :counts[b]]`` in the order of the per-image function, the other slots are zero with label -1.
+
+    ``bgs_det_candidates`` (one launch) builds all ``B * (C - 1)`` candidate lists, ``bgs_nms_batched`` /
+    ``bgs_soft_nms_batched`` run unchanged on them, ``bgs_det_select`` (two launches) writes the fixed-shape result.
+    When ``max_num`` cuts, ties between equal scores go to the earlier entry of the class-major concatenation (the
+    per-image hard-NMS arm uses ``topk``, whose tie order is unspecified).  The NMS bitmask workspace is shared by
+    the whole batch: ``B * (C - 1) * n * ceil(n / 64) * 8`` bytes, 157 MB per image of 1230 classes x 1000 rows,
+    1.26 GB for ``B = 8``.  ``n <= 4096``; ``max_num`` is required (every shipped config sets ``max_per_img``) and
+    at most 4096 after clipping to ``n * (C - 1)``."""
+    cfg = dict(nms_cfg)
+    nms_type = cfg.pop('type', 'nms')
+    if nms_type not in ('nms', 'soft_nms'):
+        raise NotImplementedError('only type="nms" and type="soft_nms" are supported (got %r)' % nms_type)
+    if max_num is None or int(max_num) <= 0:
+        raise NotImplementedError('multiclass_nms_batched returns fixed-shape rows: max_num > 0 is required '
+                                  '(got %r)' % (max_num,))
+    if nms_type == 'soft_nms':
+        method = cfg.pop('method', 'linear')
+        if method not in ('linear', 'gaussian'):
+            raise ValueError('Invalid method for SoftNMS: {}'.format(method))
+        sigma = float(cfg.pop('sigma', 0.5))
+        min_score = float(cfg.pop('min_score', 1e-3))
+    iou_thr = float(cfg.pop('iou_thr'))
+    BF._require_cuda(multi_bboxes, multi_scores, score_factors, valid)
+    assert multi_scores.dim() == 3 and multi_bboxes.dim() == 3
+    B, n, C = multi_scores.shape
+    max_num = int(max_num)
+    dev = multi_scores.device
+    k = min(max_num, n * (C - 1))
+    if B == 0 or k <= 0:
+        return (multi_bboxes.new_zeros((B, max_num, 5), dtype=torch.float32),
+                torch.full((B, max_num), -1, dtype=torch.long, device=dev),
+                torch.zeros((B,), dtype=torch.int32, device=dev))
+    dets, idx, counts = BF.det_candidates(multi_scores.float(), multi_bboxes.float(), score_thr,
+                                          'sorted' if nms_type == 'nms' else 'original', valid=valid,
+                                          score_factors=score_factors)
+    if nms_type == 'nms':
+        keep, keep_n = BF.nms_batched(dets, counts, iou_thr, iou_mode=iou_mode, max_keep=n)
+        out_dets, out_labels, out_count = BF.det_select(dets, idx, keep, keep_n, B, k)
+    else:
+        order, sel_scores, keep_n = BF.soft_nms_batched(dets, counts, iou_thr, method, sigma, min_score)
+        out_dets, out_labels, out_count = BF.det_select(dets, idx, order, keep_n, B, k, sel_scores=sel_scores)
+    out_labels = out_labels.long()
+    if k < max_num:             # max_num beyond the number of candidates: the remaining slots are unused
+        out_dets = torch.cat([out_dets, out_dets.new_zeros((B, max_num - k, 5))], dim=1)
+        out_labels = torch.cat([out_labels, out_labels.new_full((B, max_num - k), -1)], dim=1)
+    return out_dets, out_labels, out_count
+
+
+def bbox2result_batched(dets, labels, counts, num_classes):
+    """The result of :func:`multiclass_nms_batched` -> a list of ``B`` lists of ``num_classes - 1`` float32 arrays
+    (:func:`bbox2result` per image) with ONE device-to-host copy for the whole batch."""
+    B, max_num = labels.shape
+    packed = torch.cat([dets.detach().float().reshape(B, max_num * 5), labels.detach().to(torch.float32),
+                        counts.detach().view(B, 1).to(torch.float32)], dim=1).cpu().numpy()
+    out = []
+    for b in range(B):
+        k = int(packed[b, -1])
+        d = packed[b, :max_num * 5].reshape(max_num, 5)[:k]
+        lab = packed[b, max_num * 5:max_num * 6][:k].astype(np.int64)
+        out.append([d[lab == i, :] for i in range(num_classes - 1)])
+    return out
+
+
 def bbox2result(bboxes, labels, num_classes):
     """``[k,5]`` + ``[k]`` -> list of ``num_classes - 1`` float32 arrays (transforms.py:181-199)."""
     if bboxes.shape[0] == 0:

@@ -605,6 +605,36 @@ int bgs_soft_nms_batched(const float* dets, const int* counts, int P, int nmax, 
                          float sigma, float min_score, int* order, float* scores, int* keep_count,
                          bgs_stream_t stream);
 
+/* The multi-image detection tail around the two NMS entry points above (csrc/det_post.hip): B images through a
+ *   fixed number of launches and no host synchronisation; the NMS runs unchanged on P = B * (C - 1) problems.
+ *   bgs_det_candidates replaces the front of multiclass_nms (mmdet/core/post_processing/bbox_nms.py:31-49: the
+ *     per-class `scores > score_thr` mask, row selection and cat; here a torch.sort + three gathers + cat per image):
+ *     scores [B, n, C] float (column 0 = background, skipped), boxes [B, n, box_cols] float with box_cols = 4 * C
+ *     (per class) or 4 (class-agnostic), already decoded; valid [B, n] uint8 or NULL; score_factors [B, n] or NULL.
+ *     Problem p = b * (C - 1) + c - 1 gets the rows of image b with raw score[.., c] > score_thr (and valid):
+ *       mode 0 (hard NMS): in descending order of score x factor, equal keys by ascending row, NaN first
+ *                          (torch.sort(descending=True, stable=True));
+ *       mode 1 (soft-NMS): in ascending row order.
+ *     dets [P, n, 5] (x1,y1,x2,y2, score x factor), idx [P, n] int32 (row inside the image), counts [P] int32;
+ *     slots past counts[p]: zeros, idx -1 (every element is written).  One launch, no workspace.  n <= 4096 and
+ *     P * n < 2^31 (BGS_ERR_UNSUPPORTED beyond); box_cols other than 4 / 4 * C, unknown mode: BGS_ERR_INVALID_ARG.
+ *   bgs_det_select replaces the tail (bbox_nms.py:50-64: cat over the classes, `scores.sort(descending=True)`,
+ *     `[:max_num]`; here argsort / topk / boolean indexing and the host read of the result size): dets / idx of
+ *     bgs_det_candidates, keep / keep_count of bgs_nms_batched with sel_scores NULL, or order / scores / keep_count
+ *     of bgs_soft_nms_batched (keep = order, sel_scores = scores); num_problems = C - 1 problems per image.
+ *     out_dets [B, max_num, 5], out_labels [B, max_num] int32 (0-based class), out_count [B] int32 =
+ *     min(total, max_num), total = the image's survivors.  total <= max_num: class-major, inside a class by
+ *     ascending original row (hard) / in selection order (soft); total > max_num: by descending (decayed) score,
+ *     ties in class-major concatenation order.  Slots past out_count[b]: zeros, label -1.
+ *     workspace: B * 65536 bytes.  Two launches whatever B.  n <= 4096, max_num <= min(n * num_problems, 4096),
+ *     B * num_problems * n < 2^31 (BGS_ERR_UNSUPPORTED beyond). */
+int bgs_det_candidates(const float* scores, const float* boxes, const unsigned char* valid,
+                       const float* score_factors, int B, int n, int C, int box_cols, float score_thr, int mode,
+                       float* dets, int* idx, int* counts, bgs_stream_t stream);
+int bgs_det_select(const float* dets, const int* idx, const int* keep, const float* sel_scores,
+                   const int* keep_count, int B, int num_problems, int n, int max_num, float* out_dets,
+                   int* out_labels, int* out_count, void* workspace, bgs_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * Test-time augmentation (flip / multi-scale aug_test), one launch each, no workspace.  A <= 16 views; per view a
  *   HOST triple (scale s > 0, flip, width W = img_shape[1] of that view), passed to the kernel by value.

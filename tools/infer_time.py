@@ -7,6 +7,8 @@ batched NMS, max 300 dets) — informational, not the headline metric.
                                                          # (iou_thr 0.5, min_score 0.05) next to hard NMS
     python tools/infer_time.py --aug flip [iters]        # aug_test: the image and its flip (A = 2)
     python tools/infer_time.py --aug ms2flip [iters]     # aug_test: 800 x 1344 and 960 x 1600, each with its flip (A = 4)
+    python tools/infer_time.py --batch 1,2,4,8 [iters]   # simple_test_batch: ms per image for each batch size next to
+                                                         # the sequential and the pipelined simple_test loop
 """
 import os
 import sys
@@ -89,10 +91,78 @@ def aug_vs_simple(model, kind, iters, dev):
                           aug_test_ms_per_img=round(ms_aug, 3), dets=sum(r.shape[0] for r in res), iters=iters)))
 
 
+def _pipelined(model, img, iters, call):
+    """``iters`` passes with the NEXT input's trunk launched ahead (depth 2); ``call(feats)`` runs the rest."""
+    from balancedgroupsoftmax_amd import train
+    pipe = train.TrunkPipeline(model, depth=2, inference=True)
+    pipe.push(img)
+    for k in range(2 + iters):
+        if k == 2:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        feats = pipe.take()
+        pipe.push(img)
+        call(feats)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) / iters * 1e3
+    pipe.drain()
+    torch.cuda.synchronize()
+    return ms
+
+
+def batch_vs_simple(model, batches, iters, dev, rounds=3):
+    """ms per image of ``simple_test_batch`` for every batch size, with and without the next batch's trunk ahead
+    (``feats=`` from ``train.TrunkPipeline(inference=True)`` pushed with the ``[B, ...]`` tensor), next to the
+    sequential and the pipelined ``simple_test`` loop.  All arms run in this process and alternate: ``rounds`` rounds,
+    every arm once per round; the figure of an arm is the median of its rounds, the range is min .. max."""
+    import json
+    meta = dict(img_shape=(800, 1333, 3), pad_shape=(800, 1344, 3), ori_shape=(800, 1333, 3), scale_factor=1.0,
+                flip=False)
+    imgs = {B: torch.randn(B, 3, 800, 1344, device=dev) for B in sorted(set([1] + batches))}
+
+    def timed(fn, n):
+        for _ in range(2):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3
+
+    arms = [('simple_test', 1, lambda n: timed(lambda: model(imgs[1], [meta], return_loss=False, rescale=True), n)),
+            ('pipelined', 1, lambda n: _pipelined(
+                model, imgs[1], n, lambda f: model(imgs[1], [meta], return_loss=False, rescale=True, feats=f)))]
+    for B in batches:
+        metas = [meta] * B
+        arms.append(('batch%d' % B, B, lambda n, B=B, metas=metas: timed(
+            lambda: model.simple_test_batch(imgs[B], metas, rescale=True), n)))
+        arms.append(('batch%d_pipelined' % B, B, lambda n, B=B, metas=metas: _pipelined(
+            model, imgs[B], n, lambda f: model.simple_test_batch(imgs[B], metas, rescale=True, feats=f))))
+    samples = {name: [] for name, _, _ in arms}
+    for _ in range(rounds):
+        for name, B, run in arms:
+            samples[name].append(run(max(iters // B, 4)) / B)
+    res = model.simple_test_batch(imgs[max(batches)], [meta] * max(batches), rescale=True)
+    out = {}
+    for name, _, _ in arms:
+        v = sorted(samples[name])
+        out[name + '_ms_per_img'] = round(v[len(v) // 2], 3)
+        out[name + '_range'] = [round(v[0], 3), round(v[-1], 3)]
+    print(json.dumps(dict(out, batches=batches, iters=iters, rounds=rounds,
+                          dets_per_img=[sum(r.shape[0] for r in one) for one in res])))
+
+
 def main():
     argv = sys.argv[1:]
     nms = 'nms'
     aug = None
+    batches = None
+    if '--batch' in argv:
+        k = argv.index('--batch')
+        batches = [int(b) for b in argv[k + 1].split(',')]
+        del argv[k:k + 2]
+        assert batches and all(1 <= b <= 12 for b in batches), batches
     if '--aug' in argv:
         k = argv.index('--aug')
         aug = argv[k + 1]
@@ -121,6 +191,8 @@ def main():
         return soft_vs_hard(model, img, metas, iters)
     if aug is not None:
         return aug_vs_simple(model, aug, iters, dev)
+    if batches is not None:
+        return batch_vs_simple(model, batches, iters, dev)
     for _ in range(3):
         res = model(img, metas, return_loss=False, rescale=True)
     torch.cuda.synchronize()
