@@ -188,6 +188,15 @@ SIGNATURES = {
                                                                 ctypes.c_int, ctypes.c_int, c_ptr]),
     'bgs_mask_paste_u8': (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                          ctypes.c_float, ctypes.c_int, ctypes.c_int, c_ptr, c_ptr]),
+    'bgs_mask_rle_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    'bgs_mask_rle_count': (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_ptr, c_f32p,
+                                          ctypes.c_float, ctypes.c_int, ctypes.c_int, c_ptr, ctypes.c_size_t, c_ptr,
+                                          c_ptr]),
+    'bgs_mask_rle_write': (ctypes.c_int, [c_f32p, c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_ptr, c_f32p,
+                                          ctypes.c_float, ctypes.c_int, ctypes.c_int, c_ptr, ctypes.c_size_t, c_ptr,
+                                          ctypes.c_longlong, c_ptr, c_ptr, c_ptr]),
+    'bgs_rle_to_string': (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int, c_ptr, ctypes.c_longlong, c_ptr]),
+    'bgs_rle_from_string': (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int, c_ptr, ctypes.c_longlong, c_ptr]),
     'bgs_mask_gt_logits': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_ptr, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, c_f32p, c_ptr]),
     'bgs_mask_bce_partials': (ctypes.c_int, [ctypes.c_int]),

@@ -22,6 +22,7 @@
 #include <math.h>
 
 #include "bgs_common.h"
+#include "mask_sample.h"
 
 namespace {
 
@@ -188,39 +189,12 @@ __global__ __launch_bounds__(256) void mask_gt_channel_kernel(
 
 
 // ---- test-time mask paste: FCNMaskHead.get_seg_masks (mmdet/models/mask_heads/fcn_mask_head.py:125-181) without the
-// RLE step.  Per detection k: bbox = (int32)(box / scale_factor) (truncation, :164), w = max(x2 - x1 + 1, 1),
-// h likewise; bbox_mask = mmcv.imresize(prob [S, S] float32, (w, h)) = cv2.resize(..., INTER_LINEAR) on float32
-// (OpenCV resize.cpp, float path: src coordinate fx = (float)((dx + 0.5) * scale - 0.5) with scale = 1 / (w / S) in
-// double, sx = floor(fx), fx -= sx; sx < 0 -> (0, 0); sx >= S - 1 -> (S - 1, 0); rows: sy = floor(fy), the two
-// source rows clamped to [0, S - 1] with fy kept; horizontal pass first (S[sx] * (1 - fx) + S[sx + 1] * fx, or S[sx]
-// alone where sx + 1 leaves the row), then vertical (row0 * (1 - fy) + row1 * fy), all in float32, each product and sum
-// rounded separately); (bbox_mask > thr) as uint8 goes to im_mask[y1 : y1 + h, x1 : x1 + w] of a zero [img_h, img_w]
-// image.  Here the whole uint8 [K, img_h, img_w] tensor is produced in one launch — a thread owns one aligned 4-byte
-// word of it (zeros outside the boxes: no separate fill) — and the part of a box that leaves the image is clipped
-// (numpy's slice assignment raises there; boxes are clipped to the image upstream, bbox_head.py:136-139).
-__device__ __forceinline__ void paste_axis(int d, double scale, int S, int& s0, int& s1, float& f, bool rows) {
-  float fx = (float)(((double)d + 0.5) * scale - 0.5);
-  int sx = (int)floorf(fx);
-  fx -= (float)sx;
-  if (rows) {                                   // (resizeGeneric_Invoker: row indices clipped, weight kept)
-    s0 = min(max(sx, 0), S - 1);
-    s1 = min(max(sx + 1, 0), S - 1);
-    f = fx;
-    return;
-  }
-  if (sx < 0) {
-    fx = 0.f;
-    sx = 0;
-  }
-  if (sx >= S - 1) {
-    fx = 0.f;
-    sx = S - 1;
-  }
-  s0 = sx;
-  s1 = sx + 1 < S ? sx + 1 : -1;                // -1: the "D[dx] = S[sx] * ONE" tail of HResizeLinear
-  f = fx;
-}
-
+// RLE step.  The mask of a detection (box truncation, cv2's float32 INTER_LINEAR, > thr) is defined in mask_sample.h,
+// which the run-length kernels (mask_rle.hip) share; (bbox_mask > thr) as uint8 goes to
+// im_mask[y1 : y1 + h, x1 : x1 + w] of a zero [img_h, img_w] image.  Here the whole uint8 [K, img_h, img_w] tensor is
+// produced in one launch — a thread owns one aligned 4-byte word of it (zeros outside the boxes: no separate fill) —
+// and the part of a box that leaves the image is clipped (numpy's slice assignment raises there; boxes are clipped to
+// the image upstream, bbox_head.py:136-139).
 __global__ __launch_bounds__(256) void mask_paste_kernel(const float* __restrict__ probs,
                                                          const float* __restrict__ boxes, int box_stride,
                                                          int K, int S, float scale_factor, float thr, int img_h,
@@ -231,8 +205,8 @@ __global__ __launch_bounds__(256) void mask_paste_kernel(const float* __restrict
   if (b0 >= total_bytes) return;
   const long long plane = (long long)img_h * img_w;
   unsigned packed = 0;
-  int k = -1, x1 = 0, y1 = 0, w = 1, h = 1;
-  double sx_scale = 1.0, sy_scale = 1.0;
+  int k = -1;
+  bgs::PasteBox box = {0, 0, 1, 1, 1.0, 1.0};
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const long long b = b0 + t;
@@ -242,37 +216,11 @@ __global__ __launch_bounds__(256) void mask_paste_kernel(const float* __restrict
     const int y = rem / img_w, x = rem - y * img_w;
     if (kk != k) {                               // (a word crosses a detection at most once)
       k = kk;
-      const float* bx = boxes + (size_t)k * box_stride;
-      x1 = (int)(bx[0] / scale_factor);
-      y1 = (int)(bx[1] / scale_factor);
-      const int x2 = (int)(bx[2] / scale_factor), y2 = (int)(bx[3] / scale_factor);
-      w = max(x2 - x1 + 1, 1);
-      h = max(y2 - y1 + 1, 1);
-      sx_scale = 1.0 / ((double)w / (double)S);
-      sy_scale = 1.0 / ((double)h / (double)S);
+      box = bgs::paste_box(boxes + (size_t)k * box_stride, scale_factor, S);
     }
-    const int dx = x - x1, dy = y - y1;
-    if (dx < 0 || dx >= w || dy < 0 || dy >= h) continue;
-    const float* pm = probs + (size_t)k * S * S;
-    float v;
-    if (w == S && h == S) {                      // cv2.resize returns the source when the size is unchanged
-      v = pm[dy * S + dx];
-    } else {
-      int c0, c1, r0, r1;
-      float fx, fy;
-      paste_axis(dx, sx_scale, S, c0, c1, fx, false);
-      paste_axis(dy, sy_scale, S, r0, r1, fy, true);
-      const float a0 = 1.f - fx, a1 = fx, bt0 = 1.f - fy, bt1 = fy;
-      float h0, h1;
-      if (c1 >= 0) {
-        h0 = __fadd_rn(__fmul_rn(pm[r0 * S + c0], a0), __fmul_rn(pm[r0 * S + c1], a1));
-        h1 = __fadd_rn(__fmul_rn(pm[r1 * S + c0], a0), __fmul_rn(pm[r1 * S + c1], a1));
-      } else {
-        h0 = pm[r0 * S + c0];
-        h1 = pm[r1 * S + c0];
-      }
-      v = __fadd_rn(__fmul_rn(h0, bt0), __fmul_rn(h1, bt1));
-    }
+    const int dx = x - box.x1, dy = y - box.y1;
+    if (dx < 0 || dx >= box.w || dy < 0 || dy >= box.h) continue;
+    const float v = bgs::paste_value(probs + (size_t)k * S * S, S, box, dy, dx);
     if (v > thr) packed |= 1u << (8 * t);
   }
   if (b0 + 4 <= total_bytes) {

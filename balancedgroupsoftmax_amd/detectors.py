@@ -312,11 +312,33 @@ class TwoStageDetector(nn.Module):
                                                 rcnn_test_cfg.nms, rcnn_test_cfg.max_per_img)
         return det_bboxes, det_labels, scores
 
-    def simple_test(self, img, img_meta, proposals=None, rescale=False, feats=None):
+    @staticmethod
+    def _check_segm(segm):
+        if segm not in (None, 'rle'):
+            raise ValueError("segm: None (mask probabilities) or 'rle' (the reference's segm_results), got %r" % (segm,))
+        return segm is not None
+
+    def _batch_segms(self, head, probs, mask_rois, mask_labels, sizes, img_metas, rescale):
+        """The ``segm_results`` of every image of a batch: all detections encoded in one launch sequence and one size
+        read, each with its own image's ``ori_shape`` and ``scale_factor`` -> per image the reference's ``cls_segms``."""
+        rles = head.get_seg_rles(probs, mask_rois[:, 1:5], mask_labels, self.test_cfg.rcnn,
+                                 [m['ori_shape'] for m in img_metas], [m['scale_factor'] for m in img_metas], rescale,
+                                 sizes=sizes)
+        labels = mask_labels.cpu().tolist()
+        out, k0 = [], 0
+        for k in sizes:
+            out.append(head.cls_segms(rles[k0:k0 + k], labels[k0:k0 + k]))
+            k0 += k
+        return out
+
+    def simple_test(self, img, img_meta, proposals=None, rescale=False, feats=None, segm=None):
         """two_stage.py:267-289 (bbox branch): list of ``num_classes-1`` ``[k_c, 5]`` arrays.
-        ``feats``: ``extract_feat(img)`` computed ahead of this call (``train.TrunkPipeline(inference=True)``)."""
+        ``feats``: ``extract_feat(img)`` computed ahead of this call (``train.TrunkPipeline(inference=True)``).
+        With a mask branch: ``(bbox_results, probs [k, 28, 28])``, or with ``segm='rle'`` the reference's
+        ``(bbox_results, segm_results)``: per class the COCO RLE dicts in detection order."""
         from .post_processing import bbox2result
         assert self.with_bbox, 'Bbox head must be implemented.'
+        want_rle = self._check_segm(segm)
         x = self.extract_feat(img) if feats is None else feats
         proposal_list = (self.simple_test_rpn(x, img_meta, self.test_cfg.rpn)
                          if proposals is None else proposals)
@@ -325,6 +347,9 @@ class TwoStageDetector(nn.Module):
         bbox_results = bbox2result(det_bboxes, det_labels, self.bbox_head.num_classes)
         if not self.with_mask:
             return bbox_results
+        if want_rle:
+            return bbox_results, self.simple_test_mask(x, img_meta, det_bboxes, det_labels, rescale=rescale,
+                                                       paste=True, encode='rle')
         return bbox_results, self.simple_test_mask(x, img_meta, det_bboxes, det_labels,
                                                    rescale=rescale)
 
@@ -332,7 +357,8 @@ class TwoStageDetector(nn.Module):
         """test_mixins.py:153-180.  Default: the per-detection mask probabilities ``[k, 28, 28]`` of each
         detection's own class (device tensor).  ``paste=True``: the reference's return value — ``cls_segms`` of
         ``FCNMaskHead.get_seg_masks`` (per class the masks pasted into the ``ori_shape`` image, resized /
-        thresholded on the device; dense ``uint8`` unless ``encode`` produces RLEs, see ``get_seg_masks``)."""
+        thresholded on the device; dense ``uint8`` by default, ``encode='rle'`` for the reference's RLE dicts, see
+        ``get_seg_masks``)."""
         if det_bboxes.shape[0] == 0:
             if paste:
                 return [[] for _ in range(self.mask_head.num_classes - 1)]
@@ -393,15 +419,17 @@ class TwoStageDetector(nn.Module):
             labs.append(labels[b, :k])
         return torch.cat(rois), torch.cat(labs), sizes
 
-    def simple_test_batch(self, img, img_metas, proposals=None, rescale=False, feats=None):
+    def simple_test_batch(self, img, img_metas, proposals=None, rescale=False, feats=None, segm=None):
         """``simple_test`` for ``B`` images that share one padded tensor shape: ``img [B, 3, H, W]``, ``img_metas`` a
         list of ``B`` dicts (``img_shape``, ``scale_factor`` and ``ori_shape`` per image).  Returns a list of ``B``
         items, each what ``simple_test`` returns for that image.  One trunk / RPN / RoI head pass over the batch, the
         box tail of all images in a fixed number of launches (``multiclass_nms_batched``), one device-to-host copy;
         with a mask branch the mask head runs once over all images' detections after the single size read.
-        ``feats``: ``extract_feat(img)`` computed ahead (``train.TrunkPipeline(inference=True)``)."""
+        ``feats``: ``extract_feat(img)`` computed ahead (``train.TrunkPipeline(inference=True)``).  ``segm='rle'``: the
+        masks of all images are encoded together (``_batch_segms``)."""
         from .post_processing import bbox2result_batched, multiclass_nms_batched
         assert self.with_bbox, 'Bbox head must be implemented.'
+        want_rle = self._check_segm(segm)
         self._check_batch(img, img_metas)
         with torch.no_grad():
             x = self.extract_feat(img) if feats is None else feats
@@ -423,6 +451,9 @@ class TwoStageDetector(nn.Module):
                 mask_feats = self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], mask_rois)
                 probs = self.mask_head.get_mask_probs(self.mask_head.features(mask_feats, nhwc=True), mask_labels)
             results = bbox2result_batched(dets, labels, counts, self.bbox_head.num_classes)
+            if want_rle:
+                return list(zip(results, self._batch_segms(self.mask_head, probs, mask_rois, mask_labels, sizes,
+                                                           img_metas, rescale)))
             return list(zip(results, torch.split(probs, sizes)))
 
     # ------------------------------------------------------------------ test-time augmentation
@@ -500,13 +531,20 @@ class TwoStageDetector(nn.Module):
             probs.append(self.mask_head.get_mask_probs(self.mask_head.features(mask_feats, nhwc=True), det_labels))
         return merge_aug_masks(probs, img_metas, self.test_cfg.rcnn)
 
-    def aug_test(self, imgs, img_metas, rescale=False, proposals=None):
+    def _aug_segms(self, head, probs, det_bboxes, det_labels, img_metas):
+        """test_mixins.py:230-238: the merged masks pasted into the first view's ``ori_shape`` (the boxes are in the
+        original image scale: ``scale_factor=1.0, rescale=False``), as RLEs."""
+        return head.get_seg_masks(probs, det_bboxes[:, :4], det_labels, self.test_cfg.rcnn,
+                                  img_metas[0][0]['ori_shape'], 1.0, False, encode='rle')
+
+    def aug_test(self, imgs, img_metas, rescale=False, proposals=None, segm=None):
         """two_stage.py:292-319 for A views of one image.  ``rescale=False``: the boxes are multiplied by the first
         view's ``scale_factor`` (two_stage.py:305-309).  ``proposals``: merged ``[(props, valid)]`` in the original
         image scale instead of the RPN (test hook, as in ``simple_test``).  With a mask branch:
-        ``(bbox_results, probs [k, 28, 28])``."""
+        ``(bbox_results, probs [k, 28, 28])``, or ``(bbox_results, segm_results)`` with ``segm='rle'``."""
         from .post_processing import bbox2result
         assert self.with_bbox, 'Bbox head must be implemented.'
+        want_rle = self._check_segm(segm)
         self._check_aug(img_metas)
         feats = self.extract_feats(imgs)
         proposal_list = (self.aug_test_rpn(feats, img_metas, self.test_cfg.rpn)
@@ -519,7 +557,10 @@ class TwoStageDetector(nn.Module):
         bbox_results = bbox2result(_det_bboxes, det_labels, self.bbox_head.num_classes)
         if not self.with_mask:
             return bbox_results
-        return bbox_results, self.aug_test_mask(feats, img_metas, det_bboxes, det_labels)
+        probs = self.aug_test_mask(feats, img_metas, det_bboxes, det_labels)
+        if want_rle:
+            return bbox_results, self._aug_segms(self.mask_head, probs, det_bboxes, det_labels, img_metas)
+        return bbox_results, probs
 
     def forward_test(self, imgs, img_metas, **kwargs):
         """base.py:78-96.  A list of A views of one image: ``simple_test`` for one view, ``aug_test`` for more.
@@ -913,13 +954,22 @@ class HybridTaskCascade(CascadeRCNN):
         return losses
 
     # -- test time -----------------------------------------------------------------------------
-    def simple_test(self, img, img_meta, proposals=None, rescale=False, feats=None):
+    def simple_test(self, img, img_meta, proposals=None, rescale=False, feats=None, segm=None):
         """htc.py:313-432 with ``keep_all_stages=False``: the ensemble boxes (stage-averaged class
         logits) and, per detection, the mean over stages of its class's mask probability
-        ``[k, 28, 28]`` (``merge_aug_masks`` without weights; pasting / RLE is evaluation tooling)."""
+        ``[k, 28, 28]`` (``merge_aug_masks`` without weights).  ``segm='rle'``: the reference's
+        ``(bbox_results, segm_results)`` — ``get_seg_masks_without`` of the last mask head (htc.py:419-421) as COCO
+        RLE dicts."""
         from .post_processing import bbox2result
+        want_rle = self._check_segm(segm)
         det_bboxes, det_labels, masks = self.simple_test_dets(img, img_meta, proposals, rescale, feats=feats)
-        return bbox2result(det_bboxes, det_labels, self.bbox_head[-1].num_classes), masks
+        bbox_results = bbox2result(det_bboxes, det_labels, self.bbox_head[-1].num_classes)
+        if want_rle:
+            scale_factor = img_meta[0]['scale_factor']
+            boxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes[:, :4]
+            masks = self.mask_head[-1].get_seg_masks(masks, boxes, det_labels, self.test_cfg.rcnn,
+                                                     img_meta[0]['ori_shape'], scale_factor, rescale, encode='rle')
+        return bbox_results, masks
 
     def simple_test_dets(self, img, img_meta, proposals=None, rescale=False, feats=None):
         """-> ``(det_bboxes [k,5], det_labels [k], mask_probs [k,28,28])`` device tensors."""
@@ -960,11 +1010,13 @@ class HybridTaskCascade(CascadeRCNN):
     def _bbox_roi_feats(self, ext, x, rois, semantic_feat):
         return self._fused_roi_feats(ext, x, rois, semantic_feat, 'bbox')
 
-    def simple_test_batch(self, img, img_metas, proposals=None, rescale=False, feats=None):
+    def simple_test_batch(self, img, img_metas, proposals=None, rescale=False, feats=None, segm=None):
         """``simple_test`` for ``B`` images of one padded shape (see ``TwoStageDetector.simple_test_batch``): a list
         of ``B`` ``(bbox_results, probs [k_b, 28, 28])``.  The mask ensemble runs once over the detections of all
-        images, after the batch's single size read."""
+        images, after the batch's single size read.  ``segm='rle'``: ``(bbox_results, segm_results)`` per image, the
+        masks of all images encoded together."""
         from .post_processing import bbox2result_batched
+        want_rle = self._check_segm(segm)
         if self.test_cfg.get('keep_all_stages', False):
             raise NotImplementedError('keep_all_stages=True (per-stage results) is not built')
         self._check_batch(img, img_metas)
@@ -978,6 +1030,9 @@ class HybridTaskCascade(CascadeRCNN):
             else:
                 probs = self._ensemble_masks(x, mask_rois, mask_labels, semantic_feat)
             results = bbox2result_batched(dets, labels, counts, self.bbox_head[-1].num_classes)
+            if want_rle:
+                return list(zip(results, self._batch_segms(self.mask_head[-1], probs, mask_rois, mask_labels, sizes,
+                                                           img_metas, rescale)))
             return list(zip(results, torch.split(probs, sizes)))
 
     def _ensemble_masks(self, x, mask_rois, det_labels, semantic_feat):
@@ -993,14 +1048,18 @@ class HybridTaskCascade(CascadeRCNN):
             probs.append(head.get_mask_probs(head.upsample_features(last), det_labels))
         return sum(probs) / float(len(probs))
 
-    def aug_test(self, imgs, img_metas, proposals=None, rescale=False):
+    def aug_test(self, imgs, img_metas, proposals=None, rescale=False, segm=None):
         """htc.py:441-561 with ``keep_all_stages=False``: each view's semantic feature and stage loop, merged boxes
         and scores, then the mask ensemble of every stage on every view (``mask_roi_extractor[-1]`` + semantic
         fusion, mask information flow) merged over the A x stages entries, ordered by view and then by stage ->
         ``(bbox_results, probs [k, 28, 28])``.  ``rescale`` is ignored: the boxes are in the original image scale
-        (htc.py:506).  ``proposals``: merged ``[(props, valid)]`` in the original scale instead of the RPN."""
+        (htc.py:506).  ``proposals``: merged ``[(props, valid)]`` in the original scale instead of the RPN.
+        ``segm='rle'``: ``(bbox_results, segm_results)`` (htc.py:550-558)."""
         from .post_processing import bbox2result
+        want_rle = self._check_segm(segm)
         det_bboxes, det_labels, masks = self.aug_test_dets(imgs, img_metas, proposals)
+        if want_rle:
+            masks = self._aug_segms(self.mask_head[-1], masks, det_bboxes, det_labels, img_metas)
         return bbox2result(det_bboxes, det_labels, self.bbox_head[-1].num_classes), masks
 
     def aug_test_dets(self, imgs, img_metas, proposals=None):

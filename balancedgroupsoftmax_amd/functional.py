@@ -2483,6 +2483,71 @@ def mask_paste(probs, boxes, scale_factor, thr, img_h, img_w):
     return out
 
 
+def _per_detection(v, K, width, dtype):
+    """A scalar / pair, or per-detection host values (sequence, numpy, tensor) -> numpy ``[K]`` or ``[K, width]``."""
+    import numpy as np
+    if torch.is_tensor(v):
+        v = v.detach().cpu().numpy()
+    a = np.asarray(v, dtype=dtype)
+    shape = (K,) if width == 1 else (K, width)
+    if a.shape == shape:
+        return np.ascontiguousarray(a)
+    if a.shape == shape[1:]:
+        return np.ascontiguousarray(np.broadcast_to(a, shape))
+    raise ValueError('expected shape %r or %r, got %r' % (shape[1:], shape, a.shape))
+
+
+def mask_rle_counts(probs, boxes, scale_factor, thr, img_hw):
+    """The device half of :func:`mask_rle`: -> ``(counts uint32 [total], offsets int64 [K + 1], sizes int32 [K, 2])`` as
+    host numpy arrays; detection ``k``'s run lengths are ``counts[offsets[k] : offsets[k + 1]]``."""
+    import numpy as np
+    _require_cuda(probs, boxes)
+    lib = capi.load()
+    probs, boxes = _f32c(probs), _f32c(boxes)
+    K, S, S2 = probs.shape
+    assert S == S2 and boxes.dim() == 2 and boxes.shape[0] == K and boxes.shape[1] >= 4
+    hw = _per_detection(img_hw, K, 2, np.int32)
+    sf = _per_detection(scale_factor, K, 1, np.float32)
+    if K == 0:
+        return np.zeros(0, np.uint32), np.zeros(1, np.int64), hw
+    if hw.min() <= 0 or not (sf > 0).all():
+        raise ValueError('mask_rle: image sizes and scale factors must be positive')
+    max_h, max_w = int(hw[:, 0].max()), int(hw[:, 1].max())
+    dev = probs.device
+    table = torch.from_numpy(np.concatenate([hw.reshape(-1), sf.view(np.int32)])).to(dev)      # one upload
+    hw_d, sf_d = table[:2 * K], table[2 * K:].view(torch.float32)
+    ws_bytes = int(lib.bgs_mask_rle_workspace_bytes(K, max_w))
+    ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.int32, device=dev)
+    runs = torch.empty(K, dtype=torch.int32, device=dev)
+    stream = capi.current_stream(dev)
+    geom = (capi.ptr(probs), capi.ptr(boxes), int(boxes.shape[1]), K, S, capi.ptr(hw_d), capi.ptr(sf_d), float(thr),
+            max_h, max_w, capi.ptr(ws), ws_bytes)
+    capi.check('bgs_mask_rle_count', lib.bgs_mask_rle_count(*geom, capi.ptr(runs), stream))
+    offsets = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(runs, 0, dtype=torch.int64)
+    offsets_h = offsets.cpu().numpy()                      # the one synchronisation: the size of the result
+    total = int(offsets_h[-1])
+    positions = torch.empty(total, dtype=torch.int32, device=dev)
+    counts = torch.empty(total, dtype=torch.int32, device=dev)
+    capi.check('bgs_mask_rle_write', lib.bgs_mask_rle_write(*geom, capi.ptr(offsets), total, capi.ptr(positions),
+                                                            capi.ptr(counts), stream))
+    return counts.cpu().numpy().view(np.uint32), offsets_h, hw
+
+
+def mask_rle(probs, boxes, scale_factor, thr, img_hw):
+    """``FCNMaskHead.get_seg_masks`` INCLUDING the RLE step (fcn_mask_head.py:156-181) without the dense tensor
+    (``bgs_mask_rle_count`` / ``bgs_mask_rle_write`` + the host string codec): ``probs [K, S, S]``, ``boxes [K, >=4]``
+    as in :func:`mask_paste`; ``scale_factor`` a float or ``[K]``, ``img_hw`` ``(h, w)`` or ``[K, 2]`` (host values:
+    a list, numpy or a CPU tensor — per detection, so that the detections of several images go through one call).
+    Returns a list of ``K`` dicts ``{'size': [h, w], 'counts': bytes}``, the type ``pycocotools.mask.encode(m)[0]``
+    returns; ``rle.decode`` of entry ``k`` equals ``mask_paste(...)[k]``."""
+    from . import rle
+    counts, offsets, hw = mask_rle_counts(probs, boxes, scale_factor, thr, img_hw)
+    strings = rle.pack_strings(counts, offsets)
+    sizes = hw.tolist()
+    return [{'size': sizes[k], 'counts': strings[k]} for k in range(len(strings))]
+
+
 def mask_gt_logits(feat, weight, bias, labels):
     """``feat [P, pixels, C]``, ``weight [K, C]``, ``labels [P]`` -> ``[P, pixels]`` logits of each
     RoI's own class channel (no gradient: test-time / inspection path)."""

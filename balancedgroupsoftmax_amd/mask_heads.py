@@ -151,33 +151,69 @@ class FCNMaskHead(nn.Module):
                           self._channel(labels), mask_targets.reshape(P, H * W), valid)
         return dict(loss_mask=val * self.loss_mask.loss_weight)
 
+    @staticmethod
+    def seg_geometry(ori_shape, scale_factor, rescale):
+        """fcn_mask_head.py:156-161: ``(img_h, img_w, scale_factor)`` of the image the masks are pasted into."""
+        import numpy as np
+        if rescale:
+            return int(ori_shape[0]), int(ori_shape[1]), float(scale_factor)
+        # (np.round = half to even; the boxes are already in the network's scale)
+        img_h = int(np.round(ori_shape[0] * scale_factor).astype(np.int32))
+        img_w = int(np.round(ori_shape[1] * scale_factor).astype(np.int32))
+        return img_h, img_w, 1.0
+
+    def _class_probs(self, mask_pred, det_labels):
+        if mask_pred.dim() == 4:
+            ch = self._channel(det_labels + 1)
+            mask_pred = torch.sigmoid(mask_pred[torch.arange(mask_pred.size(0), device=mask_pred.device), ch])
+        return mask_pred.float()
+
     def get_seg_masks_dense(self, mask_pred, det_bboxes, det_labels, rcnn_test_cfg, ori_shape, scale_factor,
                             rescale):
         """The reference's ``get_seg_masks`` (fcn_mask_head.py:125-181) up to the RLE encoding, on the device:
         ``uint8 [n, img_h, img_w]`` with every detection's thresholded mask pasted at its (rescaled, int-truncated)
         box.  ``mask_pred``: ``[n, S, S]`` probabilities of each detection's class (``get_mask_probs``) or the
         reference's ``[n, num_classes, S, S]`` logits (the detection's channel is gathered and squashed here)."""
-        import numpy as np
-        if mask_pred.dim() == 4:
-            ch = self._channel(det_labels + 1)
-            mask_pred = torch.sigmoid(mask_pred[torch.arange(mask_pred.size(0), device=mask_pred.device), ch])
-        if rescale:
-            img_h, img_w = int(ori_shape[0]), int(ori_shape[1])
-        else:           # (:158-161: np.round = half to even; the boxes are already in the network's scale)
-            img_h = int(np.round(ori_shape[0] * scale_factor).astype(np.int32))
-            img_w = int(np.round(ori_shape[1] * scale_factor).astype(np.int32))
-            scale_factor = 1.0
-        return BF.mask_paste(mask_pred.float(), det_bboxes[:, :4], float(scale_factor),
+        img_h, img_w, scale_factor = self.seg_geometry(ori_shape, scale_factor, rescale)
+        return BF.mask_paste(self._class_probs(mask_pred, det_labels), det_bboxes[:, :4], scale_factor,
                              float(rcnn_test_cfg.mask_thr_binary), img_h, img_w)
+
+    def get_seg_rles(self, mask_pred, det_bboxes, det_labels, rcnn_test_cfg, ori_shapes, scale_factors, rescale,
+                     sizes=None):
+        """``get_seg_masks`` with the RLE step for the detections of one image or, with ``sizes`` (detections per
+        image, ``ori_shapes`` / ``scale_factors`` then lists of that length), of a whole batch in ONE launch sequence
+        and one size read (``BF.mask_rle``): a flat list of RLE dicts in detection order."""
+        import numpy as np
+        if sizes is None:
+            sizes, ori_shapes, scale_factors = [int(det_bboxes.shape[0])], [ori_shapes], [scale_factors]
+        geoms = [self.seg_geometry(o, s, rescale) for o, s in zip(ori_shapes, scale_factors)]
+        hw = np.repeat(np.array([g[:2] for g in geoms], dtype=np.int32).reshape(-1, 2), sizes, axis=0)
+        sf = np.repeat(np.array([g[2] for g in geoms], dtype=np.float32), sizes)
+        return BF.mask_rle(self._class_probs(mask_pred, det_labels), det_bboxes[:, :4], sf,
+                           float(rcnn_test_cfg.mask_thr_binary), hw)
+
+    def cls_segms(self, segms, det_labels):
+        """fcn_mask_head.py:155,179: per class the entries of ``segms`` (one per detection) in detection order."""
+        out = [[] for _ in range(self.num_classes - 1)]
+        labels = det_labels.cpu().tolist() if torch.is_tensor(det_labels) else list(det_labels)
+        for seg, lab in zip(segms, labels):
+            out[int(lab)].append(seg)
+        return out
 
     def get_seg_masks(self, mask_pred, det_bboxes, det_labels, rcnn_test_cfg, ori_shape, scale_factor, rescale,
                       encode=None):
         """Reference signature and return structure (fcn_mask_head.py:125-181): ``cls_segms[label]`` = the masks of
-        that class in detection order.  The resize / threshold / paste runs on the device
-        (``get_seg_masks_dense``); ``encode`` turns one dense ``uint8 [img_h, img_w]`` numpy mask into what the
-        caller stores — pass ``lambda m: pycocotools.mask.encode(np.asfortranarray(m[:, :, None]))[0]`` for the
-        reference's RLEs (pycocotools is evaluation tooling and not a dependency of this package); the default
-        keeps the dense masks (views of one device tensor)."""
+        that class in detection order.  ``encode='rle'``: the reference's return value, COCO RLE dicts
+        ``{'size': [h, w], 'counts': bytes}``, encoded on the device without the dense tensor
+        (``bgs_mask_rle_count`` / ``bgs_mask_rle_write``; ``rle.decode`` turns one back into a mask).  Otherwise the
+        resize / threshold / paste produces the dense tensor on the device (``get_seg_masks_dense``): the default
+        keeps the dense masks (views of one device tensor), a callable ``encode`` receives each of them as a host
+        ``uint8 [img_h, img_w]`` numpy mask and returns what the caller stores."""
+        if isinstance(encode, str):
+            if encode != 'rle':
+                raise ValueError("encode: None, a callable or 'rle' (got %r)" % (encode,))
+            return self.cls_segms(self.get_seg_rles(mask_pred, det_bboxes, det_labels, rcnn_test_cfg, ori_shape,
+                                                    scale_factor, rescale), det_labels)
         dense = self.get_seg_masks_dense(mask_pred, det_bboxes, det_labels, rcnn_test_cfg, ori_shape,
                                          scale_factor, rescale)
         cls_segms = [[] for _ in range(self.num_classes - 1)]
@@ -189,7 +225,7 @@ class FCNMaskHead(nn.Module):
 
     def get_mask_probs(self, feats, det_labels):
         """Test time: sigmoid of the detection's own class channel, ``[n, S, S]`` (the input of
-        ``get_seg_masks``' per-detection resize; RLE encoding needs pycocotools: out of scope)."""
+        ``get_seg_masks``' per-detection resize; ``get_seg_masks(..., encode='rle')`` turns them into COCO RLEs)."""
         P, H, W, C = feats.shape
         wl = self.conv_logits.weight.view(-1, C)
         z = BF.mask_gt_logits(feats.reshape(P, H * W, C), wl, self.conv_logits.bias,

@@ -829,14 +829,51 @@ int bgs_mask_target(const uint8_t* const* host_masks, const int* host_num_gt, in
 int bgs_mask_gt_logits(const float* feat, const float* weight, const float* bias,
                        const long long* labels, int P, int pixels, int C, int num_classes,
                        float* logits_out, bgs_stream_t stream);
-/* bgs_mask_paste_u8: the resize + threshold + paste of FCNMaskHead.get_seg_masks (fcn_mask_head.py:156-176; the RLE
- *   encoding that follows needs pycocotools and stays on the host): probs [K, S, S] float = sigmoid of every
+/* bgs_mask_paste_u8: the resize + threshold + paste of FCNMaskHead.get_seg_masks (fcn_mask_head.py:156-176; for the RLE
+ *   encoding that follows see bgs_mask_rle_count / bgs_mask_rle_write, which never build this tensor): probs [K, S, S] float = sigmoid of every
  *   detection's own class channel; boxes [K, box_stride >= 4] float (x1, y1, x2, y2, ...), divided by scale_factor and
  *   truncated to int32 as :164 does; out [K, img_h, img_w] uint8 in {0, 1} (every byte written; 4-byte aligned):
  *   out[k, y1 : y1 + h, x1 : x1 + w] = cv2.resize(probs[k], (w, h), INTER_LINEAR) > thr, zero elsewhere; the part of a
  *   box outside the image is clipped. */
 int bgs_mask_paste_u8(const float* probs, const float* boxes, int box_stride, int K, int S, float scale_factor,
                       float thr, int img_h, int img_w, unsigned char* out, bgs_stream_t stream);
+/* bgs_mask_rle_count / bgs_mask_rle_write (csrc/mask_rle.hip): the same resize + threshold + paste
+ *   (fcn_mask_head.py:156-176) followed by the RLE encoding of :177-178, mask_util.encode = rleEncode of pycocotools'
+ *   common/maskApi.c, WITHOUT the dense tensor.  Detection k's mask is exactly what bgs_mask_paste_u8 writes for it
+ *   with (img_h, img_w) = img_hw[k] and scale_factor = scale_factors[k] (csrc/mask_sample.h is shared), so the
+ *   detections of several images of different ori_shape go through one launch sequence.
+ *     probs [K, S, S] float (S <= 128), boxes [K, box_stride >= 4] float; img_hw [K, 2] int32; scale_factors [K]
+ *     float; max_img_h / max_img_w: HOST bounds, >= every img_hw row (rows are clamped to them); max_img_h *
+ *     max_img_w > 2^31 - 1 is BGS_ERR_UNSUPPORTED (column-major pixel indices are 32 bit, as maskApi.c's).
+ *   The mask is read in column-major order (pixel (y, x) has index x * img_h + y); counts[0] is the number of leading
+ *   zeros (0 when pixel 0 is set), the runs alternate, the last run is always emitted, an empty mask is
+ *   [img_h * img_w].
+ *   count: runs [K] int32 = the number of counts of every detection.  workspace (4-byte aligned,
+ *     >= bgs_mask_rle_workspace_bytes(K, max_img_w)) carries the per-column tallies to the write call: same
+ *     arguments, same stream order.
+ *   write: offsets [K + 1] int64 = the exclusive scan of runs (offsets[K] = total, which the caller reads once to size
+ *     the buffers); positions [total] uint32 scratch; counts [total] uint32: detection k's counts are
+ *     counts[offsets[k] : offsets[k + 1]].  No store lands outside [0, total).
+ *   K == 0 is BGS_OK.
+ * bgs_rle_to_string / bgs_rle_from_string: rleToString / rleFrString of maskApi.c on the HOST (every pointer is a
+ *   host pointer; nothing touches the device) — the 'counts' byte string of a COCO RLE dict.  Run i (minus run i - 2
+ *   for i > 2) is written as groups of 5 bits, little end first, bit 0x20 = another group follows, + 48; a run takes
+ *   at most 7 bytes (6 below 2^29).  host_offsets [K + 1] delimit the K masks in host_counts, host_str_offsets
+ *   [K + 1] the K strings in the packed byte buffer (no terminators).  to_string: BGS_ERR_INVALID_ARG when
+ *   out_capacity is too small.  from_string: host_counts == NULL only fills host_offsets (the sizing call);
+ *   malformed input is BGS_ERR_INVALID_ARG. */
+size_t bgs_mask_rle_workspace_bytes(int K, int max_img_w);
+int bgs_mask_rle_count(const float* probs, const float* boxes, int box_stride, int K, int S, const int* img_hw,
+                       const float* scale_factors, float thr, int max_img_h, int max_img_w, void* workspace,
+                       size_t workspace_bytes, int* runs, bgs_stream_t stream);
+int bgs_mask_rle_write(const float* probs, const float* boxes, int box_stride, int K, int S, const int* img_hw,
+                       const float* scale_factors, float thr, int max_img_h, int max_img_w, const void* workspace,
+                       size_t workspace_bytes, const long long* offsets, long long total, unsigned* positions,
+                       unsigned* counts, bgs_stream_t stream);
+int bgs_rle_to_string(const unsigned* host_counts, const long long* host_offsets, int K, char* host_out,
+                      long long out_capacity, long long* host_str_offsets);
+int bgs_rle_from_string(const char* host_str, const long long* host_str_offsets, int K, unsigned* host_counts,
+                        long long counts_capacity, long long* host_offsets);
 int bgs_mask_bce_partials(int P);
 int bgs_mask_bce(const float* feat, const float* weight, const float* bias, const long long* labels,
                  const float* target, const uint8_t* valid, const float* norm, int P, int pixels,
