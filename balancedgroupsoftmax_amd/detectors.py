@@ -11,11 +11,17 @@ device tensors produced by fused kernels (csrc/det_targets.hip, csrc/sampler.hip
 training iteration issues no ``.item()`` / ``nonzero()`` / D2H copy at all.  There is ONE path:
 CPU tensors raise (the tensor-op restatements used to pin the kernels are test infrastructure,
 oracle/tensor_forms.py).
+
+Test time: ``TwoStageDetector`` owns the three flows (``simple_test``, ``simple_test_batch``, ``aug_test``: checks, a
+device-tensor core, ``bbox2result``); ``CascadeRCNN`` and ``HybridTaskCascade`` supply the pieces that differ (the stage
+loop as ``_box_scores``, the per-stage mask probabilities, the semantic feature as per-pass context).
 """
 import torch
 import torch.nn as nn
 
-from . import builder
+from . import box_ops, builder, merge_augs
+from . import functional as BF
+from . import post_processing as PP
 from .registry import DETECTORS
 
 
@@ -97,7 +103,6 @@ class TwoStageDetector(nn.Module):
         ``rc`` / ``head``: the stage's rcnn config and bbox head (cascade); defaults: the
         detector's own.  ``samplers``: test hook (``dict(rcnn=fn)``: a caller-supplied draw
         instead of the device RandomSampler; oracle/tensor_forms.sampler_hooks)."""
-        from . import functional as BF
         rc = self.train_cfg.rcnn if rc is None else rc
         ac, sc = rc.assigner, rc.sampler
         N = len(proposal_list)
@@ -178,7 +183,6 @@ class TwoStageDetector(nn.Module):
         if not self.with_rpn:
             return [(p, torch.ones(p.size(0), dtype=torch.bool, device=p.device)) for p in proposals]
         cls_scores, bbox_preds = self.rpn_head(x)
-        from . import functional as BF
         self._rpn_loss_fork = None
         if fork_loss and cls_scores[0].is_cuda and BF.rpn_loss_fork_enabled() and not samplers and \
                 not (torch.is_grad_enabled() and cls_scores[0].requires_grad):
@@ -238,7 +242,6 @@ class TwoStageDetector(nn.Module):
             if not self.train_cfg.rcnn.assigner.get('gt_max_assign_all', True):
                 raise NotImplementedError('gt_max_assign_all=False')
             rois, targets = self._sample_rois_fused(proposal_list, gt_bboxes, gt_labels, samplers)
-            from . import functional as BF
             mask_fk = None
             if self.with_mask and rois.is_cuda and BF.rpn_loss_fork_enabled() and not (
                     torch.is_grad_enabled() and any(p.requires_grad for p in self.mask_head.parameters())):
@@ -290,27 +293,46 @@ class TwoStageDetector(nn.Module):
         return self.mask_head.loss_from_features(feats, mask_targets, pos_labels, valid)
 
     # ------------------------------------------------------------------ test-time path
-    def simple_test_rpn(self, x, img_meta, rpn_test_cfg):
-        """test_mixins.py:8-12; proposals stay fixed-shape ``([max_num,5], valid)`` per image."""
-        cls_scores, bbox_preds = self.rpn_head(x)
-        return self.rpn_head.get_bboxes(cls_scores, bbox_preds, img_meta, rpn_test_cfg)
+    # The three flows (one image, a batch, A views of one image) are written once, here.  A subclass supplies what
+    # differs: ``_check_test_cfg``, ``_test_context``, ``_box_scores``, ``_stage_mask_probs`` and the two heads below.
+    _last_bbox_head = property(lambda self: self.bbox_head)      # decodes the boxes; its num_classes -> bbox2result
+    _segm_head = property(lambda self: self.mask_head)           # formats the segm results
 
-    def simple_test_bboxes(self, x, img_meta, proposals, rcnn_test_cfg, rescale=False):
-        """test_mixins.py:39-67 for ONE image (the reference tests with imgs_per_gpu=1):
-        RoIAlign -> head -> merged scores + decoded boxes -> one batched 1230-class NMS."""
-        from .post_processing import multiclass_nms
-        props, valid = proposals[0] if isinstance(proposals[0], tuple) else (proposals[0], None)
-        rois = torch.cat([props.new_zeros((props.size(0), 1)), props[:, :4]], dim=1)
+    def _check_test_cfg(self):
+        """What the detector's test_cfg asks for and is not built (raised before any device work)."""
+
+    def _test_context(self, x):
+        """Per-pass context computed from the features and handed to the RoI stages (HTC: the semantic feature)."""
+        return None
+
+    def _box_scores(self, x, ctx, rois, img_metas, batched=False):
+        """The box head(s) on a set of RoIs -> ``(rois, cls_score, bbox_pred)``: the RoIs the deltas refer to, the
+        class logits and the deltas.  ``batched``: ``rois [B*n, 5]`` of the ``B`` images of ``img_metas`` (per-row
+        geometry) instead of one image's."""
         feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
-        cls_score, bbox_pred = self.bbox_head(feats, nhwc=True)
-        bboxes, scores = self.bbox_head.get_det_bboxes(
-            rois, cls_score, bbox_pred, img_meta[0]['img_shape'], img_meta[0]['scale_factor'],
-            rescale=rescale, cfg=None)
-        if valid is not None:        # padding rows of the fixed-shape proposal list never survive
-            scores = torch.where(valid[:, None], scores, scores.new_full((), -1.0))
-        det_bboxes, det_labels = multiclass_nms(bboxes, scores, rcnn_test_cfg.score_thr,
-                                                rcnn_test_cfg.nms, rcnn_test_cfg.max_per_img)
-        return det_bboxes, det_labels, scores
+        return (rois,) + tuple(self.bbox_head(feats, nhwc=True))
+
+    def _stage_mask_probs(self, x, ctx, rois, labels):
+        """One ``[k, 28, 28]`` tensor per mask head: each detection's own-class probability."""
+        feats = self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], rois)
+        return [self.mask_head.get_mask_probs(self.mask_head.features(feats, nhwc=True), labels)]
+
+    def _mask_probs(self, x, ctx, rois, labels):
+        """The mask probabilities of the final detections: the mean over the mask heads."""
+        if rois.shape[0] == 0:
+            return rois.new_zeros((0, 28, 28))
+        probs = self._stage_mask_probs(x, ctx, rois, labels)
+        return probs[0] if len(probs) == 1 else sum(probs) / float(len(probs))
+
+    @staticmethod
+    def _image_proposals(proposal_list, as_rois=True):
+        """One image's fixed-shape proposals (``[n, 5]`` or ``(props, valid)``) -> ``(rois [n, 5], valid | None)``
+        with a zero image column in front; ``as_rois=False``: the proposals as they are (aug_test maps them into
+        every view first)."""
+        props, valid = proposal_list[0] if isinstance(proposal_list[0], tuple) else (proposal_list[0], None)
+        if as_rois:
+            props = torch.cat([props.new_zeros((props.size(0), 1)), props[:, :4]], dim=1)
+        return props, valid
 
     @staticmethod
     def _check_segm(segm):
@@ -318,60 +340,73 @@ class TwoStageDetector(nn.Module):
             raise ValueError("segm: None (mask probabilities) or 'rle' (the reference's segm_results), got %r" % (segm,))
         return segm is not None
 
-    def _batch_segms(self, head, probs, mask_rois, mask_labels, sizes, img_metas, rescale):
-        """The ``segm_results`` of every image of a batch: all detections encoded in one launch sequence and one size
-        read, each with its own image's ``ori_shape`` and ``scale_factor`` -> per image the reference's ``cls_segms``."""
-        rles = head.get_seg_rles(probs, mask_rois[:, 1:5], mask_labels, self.test_cfg.rcnn,
-                                 [m['ori_shape'] for m in img_metas], [m['scale_factor'] for m in img_metas], rescale,
-                                 sizes=sizes)
-        labels = mask_labels.cpu().tolist()
-        out, k0 = [], 0
-        for k in sizes:
-            out.append(head.cls_segms(rles[k0:k0 + k], labels[k0:k0 + k]))
-            k0 += k
-        return out
+    def simple_test_rpn(self, x, img_meta, rpn_test_cfg):
+        """test_mixins.py:8-12; proposals stay fixed-shape ``([max_num,5], valid)`` per image."""
+        cls_scores, bbox_preds = self.rpn_head(x)
+        return self.rpn_head.get_bboxes(cls_scores, bbox_preds, img_meta, rpn_test_cfg)
 
-    def simple_test(self, img, img_meta, proposals=None, rescale=False, feats=None, segm=None):
-        """two_stage.py:267-289 (bbox branch): list of ``num_classes-1`` ``[k_c, 5]`` arrays.
-        ``feats``: ``extract_feat(img)`` computed ahead of this call (``train.TrunkPipeline(inference=True)``).
-        With a mask branch: ``(bbox_results, probs [k, 28, 28])``, or with ``segm='rle'`` the reference's
-        ``(bbox_results, segm_results)``: per class the COCO RLE dicts in detection order."""
-        from .post_processing import bbox2result
-        assert self.with_bbox, 'Bbox head must be implemented.'
-        want_rle = self._check_segm(segm)
-        x = self.extract_feat(img) if feats is None else feats
-        proposal_list = (self.simple_test_rpn(x, img_meta, self.test_cfg.rpn)
-                         if proposals is None else proposals)
-        det_bboxes, det_labels, _ = self.simple_test_bboxes(x, img_meta, proposal_list,
-                                                            self.test_cfg.rcnn, rescale=rescale)
-        bbox_results = bbox2result(det_bboxes, det_labels, self.bbox_head.num_classes)
-        if not self.with_mask:
-            return bbox_results
-        if want_rle:
-            return bbox_results, self.simple_test_mask(x, img_meta, det_bboxes, det_labels, rescale=rescale,
-                                                       paste=True, encode='rle')
-        return bbox_results, self.simple_test_mask(x, img_meta, det_bboxes, det_labels,
-                                                   rescale=rescale)
+    def simple_test_bboxes(self, x, img_meta, proposals, rcnn_test_cfg, rescale=False, ctx=None):
+        """test_mixins.py:39-67 for ONE image (the reference tests with imgs_per_gpu=1): RoIAlign -> head -> merged
+        scores + decoded boxes -> one batched 1230-class NMS.  The cascades (cascade_rcnn.py:300-393,
+        htc.py:313-377, ensemble result): ``_box_scores`` is their stage loop."""
+        rois, valid = self._image_proposals(proposals)
+        rois, cls_score, bbox_pred = self._box_scores(x, ctx, rois, img_meta)
+        bboxes, scores = self._last_bbox_head.get_det_bboxes(
+            rois, cls_score, bbox_pred, img_meta[0]['img_shape'], img_meta[0]['scale_factor'],
+            rescale=rescale, cfg=None)
+        if valid is not None:        # padding rows of the fixed-shape proposal list never survive
+            scores = torch.where(valid[:, None], scores, scores.new_full((), -1.0))
+        det_bboxes, det_labels = PP.multiclass_nms(bboxes, scores, rcnn_test_cfg.score_thr,
+                                                   rcnn_test_cfg.nms, rcnn_test_cfg.max_per_img)
+        return det_bboxes, det_labels, scores
 
-    def simple_test_mask(self, x, img_meta, det_bboxes, det_labels, rescale=False, paste=False, encode=None):
-        """test_mixins.py:153-180.  Default: the per-detection mask probabilities ``[k, 28, 28]`` of each
-        detection's own class (device tensor).  ``paste=True``: the reference's return value — ``cls_segms`` of
-        ``FCNMaskHead.get_seg_masks`` (per class the masks pasted into the ``ori_shape`` image, resized /
-        thresholded on the device; dense ``uint8`` by default, ``encode='rle'`` for the reference's RLE dicts, see
-        ``get_seg_masks``)."""
-        if det_bboxes.shape[0] == 0:
-            if paste:
-                return [[] for _ in range(self.mask_head.num_classes - 1)]
-            return det_bboxes.new_zeros((0, 28, 28))
+    def simple_test_mask(self, x, img_meta, det_bboxes, det_labels, rescale=False, paste=False, encode=None,
+                         ctx=None):
+        """test_mixins.py:153-180 (HTC: htc.py:379-421, the mean over the stages' heads).  Default: the
+        per-detection mask probabilities ``[k, 28, 28]`` of each detection's own class (device tensor).
+        ``paste=True``: the reference's return value — ``cls_segms`` of ``FCNMaskHead.get_seg_masks`` (per class the
+        masks pasted into the ``ori_shape`` image, resized / thresholded on the device; dense ``uint8`` by default,
+        ``encode='rle'`` for the reference's RLE dicts, see ``get_seg_masks``)."""
+        if paste and det_bboxes.shape[0] == 0:
+            return [[] for _ in range(self._segm_head.num_classes - 1)]
         boxes = det_bboxes[:, :4] * img_meta[0]['scale_factor'] if rescale else det_bboxes[:, :4]
         rois = torch.cat([boxes.new_zeros((boxes.size(0), 1)), boxes], dim=1)
-        feats = self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], rois)
-        probs = self.mask_head.get_mask_probs(self.mask_head.features(feats, nhwc=True), det_labels)
+        probs = self._mask_probs(x, ctx, rois, det_labels)
         if not paste:
             return probs
-        return self.mask_head.get_seg_masks(probs, boxes, det_labels, self.test_cfg.rcnn,
-                                            img_meta[0]['ori_shape'], img_meta[0]['scale_factor'], rescale,
-                                            encode=encode)
+        return self._segm_head.get_seg_masks(probs, boxes, det_labels, self.test_cfg.rcnn,
+                                             img_meta[0]['ori_shape'], img_meta[0]['scale_factor'], rescale,
+                                             encode=encode)
+
+    def simple_test_dets(self, img, img_meta, proposals=None, rescale=False, feats=None, segm=None):
+        """The device-tensor core of ``simple_test`` -> ``(det_bboxes [k, 5], det_labels [k], masks)``: ``masks`` is
+        ``None`` without a mask branch, the probabilities ``[k, 28, 28]``, or with ``segm='rle'`` the segm results."""
+        self._check_test_cfg()
+        x = self.extract_feat(img) if feats is None else feats      # (ahead: train.TrunkPipeline(inference=True))
+        proposal_list = (self.simple_test_rpn(x, img_meta, self.test_cfg.rpn)
+                         if proposals is None else proposals)
+        ctx = self._test_context(x)
+        det_bboxes, det_labels, _ = self.simple_test_bboxes(x, img_meta, proposal_list, self.test_cfg.rcnn,
+                                                            rescale=rescale, ctx=ctx)
+        if not self.with_mask:
+            return det_bboxes, det_labels, None
+        return det_bboxes, det_labels, self.simple_test_mask(x, img_meta, det_bboxes, det_labels, rescale=rescale,
+                                                             paste=segm is not None, encode=segm, ctx=ctx)
+
+    def simple_test(self, img, img_meta, proposals=None, rescale=False, feats=None, segm=None):
+        """two_stage.py:267-289, cascade_rcnn.py:300-393 (bbox branch, ensemble result: every stage re-regresses the
+        RoIs with its arg-max class, the class logits are averaged over the stages), htc.py:313-432 with
+        ``keep_all_stages=False``: list of ``num_classes-1`` ``[k_c, 5]`` arrays.
+        ``feats``: ``extract_feat(img)`` computed ahead of this call (``train.TrunkPipeline(inference=True)``).
+        With a mask branch: ``(bbox_results, probs [k, 28, 28])`` (HTC: the mean over stages of the detection's class
+        probability, ``merge_aug_masks`` without weights), or with ``segm='rle'`` the reference's
+        ``(bbox_results, segm_results)``: per class the COCO RLE dicts in detection order (HTC:
+        ``get_seg_masks`` of the last mask head, htc.py:419-421)."""
+        assert self.with_bbox, 'Bbox head must be implemented.'
+        self._check_segm(segm)
+        det_bboxes, det_labels, masks = self.simple_test_dets(img, img_meta, proposals, rescale, feats, segm)
+        bbox_results = PP.bbox2result(det_bboxes, det_labels, self._last_bbox_head.num_classes)
+        return bbox_results if masks is None else (bbox_results, masks)
 
     # ------------------------------------------------------------------ batched test: several images per pass
     def _check_batch(self, img, img_metas):
@@ -395,7 +430,6 @@ class TwoStageDetector(nn.Module):
     def _batch_rois(self, x, img_metas, proposals):
         """The fixed-shape proposals of the batch (the RPN's, or the caller's ``ProposalList`` / list of
         ``(props, valid)``) -> ``rois [B*n, 5]`` with the image index in column 0, ``valid [B, n]`` or ``None``."""
-        from .box_ops import rows_of
         if proposals is None:
             proposals = self.simple_test_rpn(x, img_metas, self.test_cfg.rpn)
         if hasattr(proposals, 'batched'):
@@ -405,7 +439,7 @@ class TwoStageDetector(nn.Module):
         else:
             props, valid = torch.stack(list(proposals)), None
         B, n = props.shape[:2]
-        rois = torch.cat([rows_of(range(B), n, props).view(B, n, 1), props[..., :4]], dim=2).view(B * n, 5)
+        rois = torch.cat([box_ops.rows_of(range(B), n, props).view(B, n, 1), props[..., :4]], dim=2).view(B * n, 5)
         return rois, valid
 
     def _batch_det_rows(self, dets, labels, counts, img_metas, rescale):
@@ -419,40 +453,50 @@ class TwoStageDetector(nn.Module):
             labs.append(labels[b, :k])
         return torch.cat(rois), torch.cat(labs), sizes
 
+    def _batch_segms(self, head, probs, mask_rois, mask_labels, sizes, img_metas, rescale):
+        """The ``segm_results`` of every image of a batch: all detections encoded in one launch sequence and one size
+        read, each with its own image's ``ori_shape`` and ``scale_factor`` -> per image the reference's ``cls_segms``."""
+        rles = head.get_seg_rles(probs, mask_rois[:, 1:5], mask_labels, self.test_cfg.rcnn,
+                                 [m['ori_shape'] for m in img_metas], [m['scale_factor'] for m in img_metas], rescale,
+                                 sizes=sizes)
+        labels = mask_labels.cpu().tolist()
+        out, k0 = [], 0
+        for k in sizes:
+            out.append(head.cls_segms(rles[k0:k0 + k], labels[k0:k0 + k]))
+            k0 += k
+        return out
+
     def simple_test_batch(self, img, img_metas, proposals=None, rescale=False, feats=None, segm=None):
         """``simple_test`` for ``B`` images that share one padded tensor shape: ``img [B, 3, H, W]``, ``img_metas`` a
         list of ``B`` dicts (``img_shape``, ``scale_factor`` and ``ori_shape`` per image).  Returns a list of ``B``
-        items, each what ``simple_test`` returns for that image.  One trunk / RPN / RoI head pass over the batch, the
-        box tail of all images in a fixed number of launches (``multiclass_nms_batched``), one device-to-host copy;
-        with a mask branch the mask head runs once over all images' detections after the single size read.
+        items, each what ``simple_test`` returns for that image.  One trunk / RPN / RoI head pass over the batch
+        (the cascades: the stage loop over the ``[B*n, 5]`` rois, per-row geometry), the box tail of all images in a
+        fixed number of launches (``multiclass_nms_batched``), one device-to-host copy; with a mask branch the mask
+        head(s) run once over all images' detections after the single size read.
         ``feats``: ``extract_feat(img)`` computed ahead (``train.TrunkPipeline(inference=True)``).  ``segm='rle'``: the
         masks of all images are encoded together (``_batch_segms``)."""
-        from .post_processing import bbox2result_batched, multiclass_nms_batched
         assert self.with_bbox, 'Bbox head must be implemented.'
         want_rle = self._check_segm(segm)
+        self._check_test_cfg()
         self._check_batch(img, img_metas)
         with torch.no_grad():
             x = self.extract_feat(img) if feats is None else feats
+            ctx = self._test_context(x)
             rois, valid = self._batch_rois(x, img_metas, proposals)
-            roi_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
-            cls_score, bbox_pred = self.bbox_head(roi_feats, nhwc=True)
-            bboxes, scores = self.bbox_head.get_det_bboxes_batched(
+            rois, cls_score, bbox_pred = self._box_scores(x, ctx, rois, img_metas, batched=True)
+            bboxes, scores = self._last_bbox_head.get_det_bboxes_batched(
                 rois, cls_score, bbox_pred, [m['img_shape'] for m in img_metas],
                 [m['scale_factor'] for m in img_metas], rescale=rescale)
             cfg = self.test_cfg.rcnn
-            dets, labels, counts = multiclass_nms_batched(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img,
-                                                          valid=valid)
+            dets, labels, counts = PP.multiclass_nms_batched(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img,
+                                                             valid=valid)
             if not self.with_mask:
-                return bbox2result_batched(dets, labels, counts, self.bbox_head.num_classes)
+                return PP.bbox2result_batched(dets, labels, counts, self._last_bbox_head.num_classes)
             mask_rois, mask_labels, sizes = self._batch_det_rows(dets, labels, counts, img_metas, rescale)
-            if mask_rois.shape[0] == 0:
-                probs = mask_rois.new_zeros((0, 28, 28))
-            else:
-                mask_feats = self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], mask_rois)
-                probs = self.mask_head.get_mask_probs(self.mask_head.features(mask_feats, nhwc=True), mask_labels)
-            results = bbox2result_batched(dets, labels, counts, self.bbox_head.num_classes)
+            probs = self._mask_probs(x, ctx, mask_rois, mask_labels)
+            results = PP.bbox2result_batched(dets, labels, counts, self._last_bbox_head.num_classes)
             if want_rle:
-                return list(zip(results, self._batch_segms(self.mask_head, probs, mask_rois, mask_labels, sizes,
+                return list(zip(results, self._batch_segms(self._segm_head, probs, mask_rois, mask_labels, sizes,
                                                            img_metas, rescale)))
             return list(zip(results, torch.split(probs, sizes)))
 
@@ -465,7 +509,6 @@ class TwoStageDetector(nn.Module):
 
     def _check_aug(self, img_metas):
         """The limits of aug_test, raised before any device work."""
-        from . import functional as BF
         A = len(img_metas)
         if A > BF.AUG_MAX_VIEWS:
             raise NotImplementedError('aug_test: at most %d views (got %d)' % (BF.AUG_MAX_VIEWS, A))
@@ -486,81 +529,78 @@ class TwoStageDetector(nn.Module):
     def aug_test_rpn(self, feats, img_metas, rpn_test_cfg):
         """test_mixins.py:14-34 for one image: every view's fixed-shape proposals, merged in the original image
         scale (``merge_augs.merge_aug_proposals``) -> ``[(props [max_num, 5], valid [max_num])]``."""
-        from .merge_augs import merge_aug_proposals
         views = [self.simple_test_rpn(x, meta, rpn_test_cfg)[0] for x, meta in zip(feats, img_metas)]
-        return [merge_aug_proposals(views, img_metas, rpn_test_cfg)]
+        return [merge_augs.merge_aug_proposals(views, img_metas, rpn_test_cfg)]
 
-    @staticmethod
-    def _split_proposals(proposal_list):
-        props, valid = proposal_list[0] if isinstance(proposal_list[0], tuple) else (proposal_list[0], None)
-        return props, valid
-
-    def aug_test_bboxes(self, feats, img_metas, proposal_list, rcnn_test_cfg):
-        """test_mixins.py:138-173: the merged proposals mapped into every view (one launch), the box head per view,
-        boxes mapped back and averaged with the scores (one launch), then ``multiclass_nms``."""
-        from . import functional as BF
-        from .merge_augs import merge_aug_bboxes
-        from .post_processing import multiclass_nms
-        props, valid = self._split_proposals(proposal_list)
+    def aug_test_bboxes(self, feats, img_metas, proposal_list, rcnn_test_cfg, ctxs=None):
+        """test_mixins.py:138-173 (the cascades: cascade_rcnn.py:445-503 / htc.py:441-504): the merged proposals
+        mapped into every view (one launch), the box head(s) per view against that view's ``img_meta``, boxes mapped
+        back and averaged with the scores (one launch), then ``multiclass_nms``."""
+        props, valid = self._image_proposals(proposal_list, as_rois=False)
         A = len(feats)
         rois_all = BF.aug_map_boxes([props] * A, self._view_geoms(img_metas), back=False, mode='rois')
         aug_bboxes, aug_scores = [], []
         for a, (x, meta) in enumerate(zip(feats, img_metas)):
-            rois = rois_all[a]
-            roi_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
-            cls_score, bbox_pred = self.bbox_head(roi_feats, nhwc=True)
-            bboxes, scores = self.bbox_head.get_det_bboxes(rois, cls_score, bbox_pred, meta[0]['img_shape'],
-                                                           meta[0]['scale_factor'], rescale=False, cfg=None)
+            rois, cls_score, bbox_pred = self._box_scores(x, ctxs[a] if ctxs else None, rois_all[a], meta)
+            bboxes, scores = self._last_bbox_head.get_det_bboxes(rois, cls_score, bbox_pred, meta[0]['img_shape'],
+                                                                 meta[0]['scale_factor'], rescale=False, cfg=None)
             aug_bboxes.append(bboxes)
             aug_scores.append(scores)
-        bboxes, scores = merge_aug_bboxes(aug_bboxes, aug_scores, img_metas, rcnn_test_cfg, valid=valid)
-        return multiclass_nms(bboxes, scores, rcnn_test_cfg.score_thr, rcnn_test_cfg.nms, rcnn_test_cfg.max_per_img)
+        bboxes, scores = merge_augs.merge_aug_bboxes(aug_bboxes, aug_scores, img_metas, rcnn_test_cfg, valid=valid)
+        return PP.multiclass_nms(bboxes, scores, rcnn_test_cfg.score_thr, rcnn_test_cfg.nms,
+                                 rcnn_test_cfg.max_per_img)
 
-    def aug_test_mask(self, feats, img_metas, det_bboxes, det_labels):
-        """test_mixins.py:207-239 up to ``get_seg_masks``: per detection the merged probability of its own class
-        ``[k, 28, 28]`` (what ``simple_test_mask`` returns); ``det_bboxes`` are in the original image scale."""
-        from . import functional as BF
-        from .merge_augs import merge_aug_masks
+    def aug_test_mask(self, feats, img_metas, det_bboxes, det_labels, ctxs=None):
+        """test_mixins.py:207-239 up to ``get_seg_masks`` (HTC: htc.py:510-549, every stage's head on every view,
+        merged over the A x stages entries ordered by view and then by stage): per detection the merged probability
+        of its own class ``[k, 28, 28]`` (what ``simple_test_mask`` returns); ``det_bboxes`` are in the original
+        image scale."""
         if det_bboxes.shape[0] == 0:
             return det_bboxes.new_zeros((0, 28, 28))
         A = len(feats)
         rois_all = BF.aug_map_boxes([det_bboxes[:, :4]] * A, self._view_geoms(img_metas), back=False, mode='rois')
-        probs = []
-        for a, x in enumerate(feats):
-            mask_feats = self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], rois_all[a])
-            probs.append(self.mask_head.get_mask_probs(self.mask_head.features(mask_feats, nhwc=True), det_labels))
-        return merge_aug_masks(probs, img_metas, self.test_cfg.rcnn)
+        probs, entry_metas = [], []
+        for a, (x, meta) in enumerate(zip(feats, img_metas)):
+            stages = self._stage_mask_probs(x, ctxs[a] if ctxs else None, rois_all[a], det_labels)
+            probs += stages
+            entry_metas += [meta] * len(stages)
+        return merge_augs.merge_aug_masks(probs, entry_metas, self.test_cfg.rcnn)
 
     def _aug_segms(self, head, probs, det_bboxes, det_labels, img_metas):
-        """test_mixins.py:230-238: the merged masks pasted into the first view's ``ori_shape`` (the boxes are in the
-        original image scale: ``scale_factor=1.0, rescale=False``), as RLEs."""
+        """test_mixins.py:230-238 (htc.py:550-558): the merged masks pasted into the first view's ``ori_shape`` (the
+        boxes are in the original image scale: ``scale_factor=1.0, rescale=False``), as RLEs."""
         return head.get_seg_masks(probs, det_bboxes[:, :4], det_labels, self.test_cfg.rcnn,
                                   img_metas[0][0]['ori_shape'], 1.0, False, encode='rle')
+
+    def aug_test_dets(self, imgs, img_metas, proposals=None, segm=None):
+        """The device-tensor core of ``aug_test`` -> ``(det_bboxes [k, 5], det_labels [k], masks)`` in the original
+        image scale; ``masks`` as in ``simple_test_dets``."""
+        self._check_test_cfg()
+        self._check_aug(img_metas)
+        feats = self.extract_feats(imgs)
+        ctxs = [self._test_context(x) for x in feats]
+        proposal_list = (self.aug_test_rpn(feats, img_metas, self.test_cfg.rpn)
+                         if proposals is None else proposals)
+        det_bboxes, det_labels = self.aug_test_bboxes(feats, img_metas, proposal_list, self.test_cfg.rcnn, ctxs)
+        if not self.with_mask:
+            return det_bboxes, det_labels, None
+        masks = self.aug_test_mask(feats, img_metas, det_bboxes, det_labels, ctxs)
+        if segm is not None:
+            masks = self._aug_segms(self._segm_head, masks, det_bboxes, det_labels, img_metas)
+        return det_bboxes, det_labels, masks
 
     def aug_test(self, imgs, img_metas, rescale=False, proposals=None, segm=None):
         """two_stage.py:292-319 for A views of one image.  ``rescale=False``: the boxes are multiplied by the first
         view's ``scale_factor`` (two_stage.py:305-309).  ``proposals``: merged ``[(props, valid)]`` in the original
         image scale instead of the RPN (test hook, as in ``simple_test``).  With a mask branch:
         ``(bbox_results, probs [k, 28, 28])``, or ``(bbox_results, segm_results)`` with ``segm='rle'``."""
-        from .post_processing import bbox2result
         assert self.with_bbox, 'Bbox head must be implemented.'
-        want_rle = self._check_segm(segm)
-        self._check_aug(img_metas)
-        feats = self.extract_feats(imgs)
-        proposal_list = (self.aug_test_rpn(feats, img_metas, self.test_cfg.rpn)
-                         if proposals is None else proposals)
-        det_bboxes, det_labels = self.aug_test_bboxes(feats, img_metas, proposal_list, self.test_cfg.rcnn)
-        if rescale:
-            _det_bboxes = det_bboxes
-        else:
-            _det_bboxes = torch.cat([det_bboxes[:, :4] * img_metas[0][0]['scale_factor'], det_bboxes[:, 4:]], dim=1)
-        bbox_results = bbox2result(_det_bboxes, det_labels, self.bbox_head.num_classes)
-        if not self.with_mask:
-            return bbox_results
-        probs = self.aug_test_mask(feats, img_metas, det_bboxes, det_labels)
-        if want_rle:
-            return bbox_results, self._aug_segms(self.mask_head, probs, det_bboxes, det_labels, img_metas)
-        return bbox_results, probs
+        self._check_segm(segm)
+        det_bboxes, det_labels, masks = self.aug_test_dets(imgs, img_metas, proposals, segm)
+        if not rescale:
+            det_bboxes = torch.cat([det_bboxes[:, :4] * img_metas[0][0]['scale_factor'], det_bboxes[:, 4:]], dim=1)
+        bbox_results = PP.bbox2result(det_bboxes, det_labels, self._last_bbox_head.num_classes)
+        return bbox_results if masks is None else (bbox_results, masks)
 
     def forward_test(self, imgs, img_metas, **kwargs):
         """base.py:78-96.  A list of A views of one image: ``simple_test`` for one view, ``aug_test`` for more.
@@ -665,7 +705,6 @@ class CascadeRCNN(TwoStageDetector):
     def _refined_proposals(self, head, rois, labels, bbox_pred, img_meta, num):
         """``refine_bboxes`` (bbox_head.py:169-208) in fixed shape: every sampled RoI re-regressed
         with its target class; GT rows and padding slots are masked instead of removed."""
-        from . import functional as BF
         n_img = len(img_meta)
         with torch.no_grad():
             # regress_by_class + delta2bbox for every image in ONE launch (csrc/det_targets.hip:
@@ -704,120 +743,38 @@ class CascadeRCNN(TwoStageDetector):
         self._join_rpn_loss()
         return losses
 
-    def simple_test(self, img, img_meta, proposals=None, rescale=False, feats=None):
-        """cascade_rcnn.py:300-393 (bbox branch, ensemble result): every stage re-regresses the
-        1000 RoIs with its arg-max class, the class logits are averaged over the stages."""
-        from .post_processing import bbox2result, multiclass_nms
-        x = self.extract_feat(img) if feats is None else feats      # (ahead: train.TrunkPipeline(inference=True))
-        proposal_list = (self.simple_test_rpn(x, img_meta, self.test_cfg.rpn)
-                         if proposals is None else proposals)
-        props, valid = proposal_list[0] if isinstance(proposal_list[0], tuple) \
-            else (proposal_list[0], None)
-        rois = torch.cat([props.new_zeros((props.size(0), 1)), props[:, :4]], dim=1)
-        ms_scores = []
-        for i in range(self.num_stages):
-            head, ext = self.bbox_head[i], self.bbox_roi_extractor[i]
-            cls_score, bbox_pred = head(ext(x[:ext.num_inputs], rois), nhwc=True)
-            ms_scores.append(cls_score)
-            if i < self.num_stages - 1:
-                bbox_label = cls_score.argmax(dim=1)
-                rois = head.regress_by_class(rois, bbox_label, bbox_pred, img_meta[0])
-        cls_score = sum(ms_scores) / float(self.num_stages)
-        bboxes, scores = self.bbox_head[-1].get_det_bboxes(
-            rois, cls_score, bbox_pred, img_meta[0]['img_shape'], img_meta[0]['scale_factor'],
-            rescale=rescale, cfg=None)
-        if valid is not None:
-            scores = torch.where(valid[:, None], scores, scores.new_full((), -1.0))
-        cfg = self.test_cfg.rcnn
-        det_bboxes, det_labels = multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms,
-                                                cfg.max_per_img)
-        return bbox2result(det_bboxes, det_labels, self.bbox_head[-1].num_classes)
+    # -- test time: TwoStageDetector's flows with the stage loop as the box scores ------------------------
+    _last_bbox_head = property(lambda self: self.bbox_head[-1])
+    _segm_head = property(lambda self: self.mask_head[-1])
 
-    def _stage_loop(self, x, rois, img_meta, semantic_feat=None):
-        """One view's test-time stage loop (``simple_test``): every stage re-regresses the RoIs with its arg-max
-        class against this view's ``img_meta``; the class logits are averaged over the stages ->
-        ``(bboxes, scores)`` in the view's scale (``get_det_bboxes``, ``rescale=False``)."""
-        ms_scores = []
-        for i in range(self.num_stages):
-            head, ext = self.bbox_head[i], self.bbox_roi_extractor[i]
-            if semantic_feat is None:
-                feats = ext(x[:ext.num_inputs], rois)
-            else:
-                feats = self._fused_roi_feats(ext, x, rois, semantic_feat, 'bbox')
-            cls_score, bbox_pred = head(feats, nhwc=True)
-            ms_scores.append(cls_score)
-            if i < self.num_stages - 1:
-                rois = head.regress_by_class(rois, cls_score.argmax(dim=1), bbox_pred, img_meta[0])
-        cls_score = sum(ms_scores) / float(len(ms_scores))
-        return self.bbox_head[-1].get_det_bboxes(rois, cls_score, bbox_pred, img_meta[0]['img_shape'],
-                                                 img_meta[0]['scale_factor'], rescale=False, cfg=None)
-
-    def _bbox_roi_feats(self, ext, x, rois, semantic_feat):
+    def _bbox_roi_feats(self, ext, x, rois, ctx):
         return ext(x[:ext.num_inputs], rois)
 
-    def _batch_dets(self, x, img_metas, proposals, rescale, semantic_feat=None):
-        """The stage loop of ``simple_test`` over the ``[B*n, 5]`` rois of a batch (every stage re-regresses with its
-        arg-max class against the row's own image shape: ``regress_by_class_batched``), the stage-averaged logits,
-        ``get_det_bboxes_batched`` and the batched box tail -> ``(dets, labels, counts)`` of
-        ``multiclass_nms_batched``."""
-        from .box_ops import rows_of
-        from .post_processing import multiclass_nms_batched
-        rois, valid = self._batch_rois(x, img_metas, proposals)
-        n = rois.size(0) // len(img_metas)
-        wmax = rows_of([m['img_shape'][1] - 1 for m in img_metas], n, rois)
-        hmax = rows_of([m['img_shape'][0] - 1 for m in img_metas], n, rois)
+    def _box_scores(self, x, ctx, rois, img_metas, batched=False):
+        """The test-time stage loop (cascade_rcnn.py:326-382 and :467-487 / htc.py:327-371 and :472-486): every stage
+        re-regresses the RoIs with its arg-max class — against the one image's ``img_meta`` (``regress_by_class``), or ``batched`` against
+        each row's own image shape (``regress_by_class_batched``) — and the class logits are averaged over the
+        stages -> ``(last stage's rois, mean cls_score, last stage's bbox_pred)``."""
+        if batched:
+            n = rois.size(0) // len(img_metas)
+            wmax = box_ops.rows_of([m['img_shape'][1] - 1 for m in img_metas], n, rois)
+            hmax = box_ops.rows_of([m['img_shape'][0] - 1 for m in img_metas], n, rois)
         ms_scores = []
         for i in range(self.num_stages):
             head, ext = self.bbox_head[i], self.bbox_roi_extractor[i]
-            cls_score, bbox_pred = head(self._bbox_roi_feats(ext, x, rois, semantic_feat), nhwc=True)
+            cls_score, bbox_pred = head(self._bbox_roi_feats(ext, x, rois, ctx), nhwc=True)
             ms_scores.append(cls_score)
             if i < self.num_stages - 1:
-                rois = head.regress_by_class_batched(rois, cls_score.argmax(dim=1), bbox_pred, wmax, hmax)
-        cls_score = sum(ms_scores) / float(self.num_stages)
-        bboxes, scores = self.bbox_head[-1].get_det_bboxes_batched(
-            rois, cls_score, bbox_pred, [m['img_shape'] for m in img_metas],
-            [m['scale_factor'] for m in img_metas], rescale=rescale)
-        cfg = self.test_cfg.rcnn
-        return multiclass_nms_batched(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img, valid=valid)
+                label = cls_score.argmax(dim=1)
+                rois = (head.regress_by_class_batched(rois, label, bbox_pred, wmax, hmax) if batched
+                        else head.regress_by_class(rois, label, bbox_pred, img_metas[0]))
+        return rois, sum(ms_scores) / float(len(ms_scores)), bbox_pred
 
-    def simple_test_batch(self, img, img_metas, proposals=None, rescale=False, feats=None):
-        """``simple_test`` for ``B`` images of one padded shape (see ``TwoStageDetector.simple_test_batch``): a list
-        of ``B`` ``bbox_results``."""
-        from .post_processing import bbox2result_batched
-        self._check_batch(img, img_metas)
-        with torch.no_grad():
-            x = self.extract_feat(img) if feats is None else feats
-            dets, labels, counts = self._batch_dets(x, img_metas, proposals, rescale)
-            return bbox2result_batched(dets, labels, counts, self.bbox_head[-1].num_classes)
-
-    def _aug_test_dets(self, feats, img_metas, proposals, semantic_feats):
-        """cascade_rcnn.py:445-503 / htc.py:441-504: merged proposals (or the caller's, original scale) mapped into
-        every view, each view's stage loop, boxes and scores merged, ``multiclass_nms``."""
-        from . import functional as BF
-        from .merge_augs import merge_aug_bboxes
-        from .post_processing import multiclass_nms
-        proposal_list = (self.aug_test_rpn(feats, img_metas, self.test_cfg.rpn)
-                         if proposals is None else proposals)
-        props, valid = self._split_proposals(proposal_list)
-        rois_all = BF.aug_map_boxes([props] * len(feats), self._view_geoms(img_metas), back=False, mode='rois')
-        aug_bboxes, aug_scores = [], []
-        for a, (x, meta) in enumerate(zip(feats, img_metas)):
-            bboxes, scores = self._stage_loop(x, rois_all[a], meta, semantic_feats[a])
-            aug_bboxes.append(bboxes)
-            aug_scores.append(scores)
-        bboxes, scores = merge_aug_bboxes(aug_bboxes, aug_scores, img_metas, self.test_cfg.rcnn, valid=valid)
-        cfg = self.test_cfg.rcnn
-        return multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
-
-    def aug_test(self, imgs, img_metas, proposals=None, rescale=False):
-        """cascade_rcnn.py:445-548 (bbox branch): ``rescale`` is ignored, the boxes are in the original image scale
-        (cascade_rcnn.py:507).  ``proposals``: merged ``[(props, valid)]`` in the original scale instead of the
-        RPN."""
-        from .post_processing import bbox2result
-        self._check_aug(img_metas)
-        feats = self.extract_feats(imgs)
-        det_bboxes, det_labels = self._aug_test_dets(feats, img_metas, proposals, [None] * len(feats))
-        return bbox2result(det_bboxes, det_labels, self.bbox_head[-1].num_classes)
+    def aug_test(self, imgs, img_metas, proposals=None, rescale=False, segm=None):
+        """cascade_rcnn.py:445-548 / htc.py:441-561 with ``keep_all_stages=False``, in the reference's argument
+        order: ``rescale`` is ignored, the boxes are in the original image scale (cascade_rcnn.py:507, htc.py:506).
+        ``proposals``: merged ``[(props, valid)]`` in the original scale instead of the RPN."""
+        return super().aug_test(imgs, img_metas, True, proposals, segm)
 
 
 @DETECTORS.register_module
@@ -953,141 +910,31 @@ class HybridTaskCascade(CascadeRCNN):
         self._join_rpn_loss()
         return losses
 
-    # -- test time -----------------------------------------------------------------------------
-    def simple_test(self, img, img_meta, proposals=None, rescale=False, feats=None, segm=None):
-        """htc.py:313-432 with ``keep_all_stages=False``: the ensemble boxes (stage-averaged class
-        logits) and, per detection, the mean over stages of its class's mask probability
-        ``[k, 28, 28]`` (``merge_aug_masks`` without weights).  ``segm='rle'``: the reference's
-        ``(bbox_results, segm_results)`` — ``get_seg_masks_without`` of the last mask head (htc.py:419-421) as COCO
-        RLE dicts."""
-        from .post_processing import bbox2result
-        want_rle = self._check_segm(segm)
-        det_bboxes, det_labels, masks = self.simple_test_dets(img, img_meta, proposals, rescale, feats=feats)
-        bbox_results = bbox2result(det_bboxes, det_labels, self.bbox_head[-1].num_classes)
-        if want_rle:
-            scale_factor = img_meta[0]['scale_factor']
-            boxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes[:, :4]
-            masks = self.mask_head[-1].get_seg_masks(masks, boxes, det_labels, self.test_cfg.rcnn,
-                                                     img_meta[0]['ori_shape'], scale_factor, rescale, encode='rle')
-        return bbox_results, masks
-
-    def simple_test_dets(self, img, img_meta, proposals=None, rescale=False, feats=None):
-        """-> ``(det_bboxes [k,5], det_labels [k], mask_probs [k,28,28])`` device tensors."""
-        from .post_processing import multiclass_nms
+    # -- test time: the flows are TwoStageDetector's, the stage loop CascadeRCNN's ---------------------------
+    def _check_test_cfg(self):
         if self.test_cfg.get('keep_all_stages', False):
             raise NotImplementedError('keep_all_stages=True (per-stage results) is not built')
-        x = self.extract_feat(img) if feats is None else feats      # (ahead: train.TrunkPipeline(inference=True))
-        proposal_list = (self.simple_test_rpn(x, img_meta, self.test_cfg.rpn)
-                         if proposals is None else proposals)
-        semantic_feat = self.semantic_head(x)[1] if self.with_semantic else None
-        props, valid = proposal_list[0] if isinstance(proposal_list[0], tuple) \
-            else (proposal_list[0], None)
-        rois = torch.cat([props.new_zeros((props.size(0), 1)), props[:, :4]], dim=1)
-        ms_scores = []
-        for i in range(self.num_stages):
-            head, ext = self.bbox_head[i], self.bbox_roi_extractor[i]
-            cls_score, bbox_pred = head(self._fused_roi_feats(ext, x, rois, semantic_feat, 'bbox'),
-                                        nhwc=True)
-            ms_scores.append(cls_score)
-            if i < self.num_stages - 1:
-                rois = head.regress_by_class(rois, cls_score.argmax(dim=1), bbox_pred, img_meta[0])
-        cls_score = sum(ms_scores) / float(len(ms_scores))
-        scale_factor = img_meta[0]['scale_factor']
-        bboxes, scores = self.bbox_head[-1].get_det_bboxes(
-            rois, cls_score, bbox_pred, img_meta[0]['img_shape'], scale_factor, rescale=rescale,
-            cfg=None)
-        if valid is not None:
-            scores = torch.where(valid[:, None], scores, scores.new_full((), -1.0))
-        cfg = self.test_cfg.rcnn
-        det_bboxes, det_labels = multiclass_nms(bboxes, scores, cfg.score_thr, cfg.nms,
-                                                cfg.max_per_img)
-        if det_bboxes.shape[0] == 0:
-            return det_bboxes, det_labels, det_bboxes.new_zeros((0, 28, 28))
-        boxes = det_bboxes[:, :4] * scale_factor if rescale else det_bboxes[:, :4]
-        mask_rois = torch.cat([boxes.new_zeros((boxes.size(0), 1)), boxes], dim=1)
-        return det_bboxes, det_labels, self._ensemble_masks(x, mask_rois, det_labels, semantic_feat)
+
+    def _test_context(self, x):
+        return self.semantic_head(x)[1] if self.with_semantic else None
 
     def _bbox_roi_feats(self, ext, x, rois, semantic_feat):
         return self._fused_roi_feats(ext, x, rois, semantic_feat, 'bbox')
 
-    def simple_test_batch(self, img, img_metas, proposals=None, rescale=False, feats=None, segm=None):
-        """``simple_test`` for ``B`` images of one padded shape (see ``TwoStageDetector.simple_test_batch``): a list
-        of ``B`` ``(bbox_results, probs [k_b, 28, 28])``.  The mask ensemble runs once over the detections of all
-        images, after the batch's single size read.  ``segm='rle'``: ``(bbox_results, segm_results)`` per image, the
-        masks of all images encoded together."""
-        from .post_processing import bbox2result_batched
-        want_rle = self._check_segm(segm)
-        if self.test_cfg.get('keep_all_stages', False):
-            raise NotImplementedError('keep_all_stages=True (per-stage results) is not built')
-        self._check_batch(img, img_metas)
-        with torch.no_grad():
-            x = self.extract_feat(img) if feats is None else feats
-            semantic_feat = self.semantic_head(x)[1] if self.with_semantic else None
-            dets, labels, counts = self._batch_dets(x, img_metas, proposals, rescale, semantic_feat)
-            mask_rois, mask_labels, sizes = self._batch_det_rows(dets, labels, counts, img_metas, rescale)
-            if mask_rois.shape[0] == 0:
-                probs = mask_rois.new_zeros((0, 28, 28))
-            else:
-                probs = self._ensemble_masks(x, mask_rois, mask_labels, semantic_feat)
-            results = bbox2result_batched(dets, labels, counts, self.bbox_head[-1].num_classes)
-            if want_rle:
-                return list(zip(results, self._batch_segms(self.mask_head[-1], probs, mask_rois, mask_labels, sizes,
-                                                           img_metas, rescale)))
-            return list(zip(results, torch.split(probs, sizes)))
-
-    def _ensemble_masks(self, x, mask_rois, det_labels, semantic_feat):
-        """htc.py:379-405: every stage's mask head on the final boxes' features (mask information
-        flow through ``conv_res``), mean of the per-class probabilities."""
-        mask_feats = self._fused_roi_feats(self.mask_roi_extractor[-1], x, mask_rois, semantic_feat,
-                                           'mask')
+    def _stage_mask_probs(self, x, semantic_feat, rois, labels):
+        """htc.py:379-405 and :525-546: every stage's mask head on the final boxes' features
+        (``mask_roi_extractor[-1]`` + semantic fusion, mask information flow through ``conv_res``) -> one ``[k, 28, 28]`` per stage."""
+        mask_feats = self._fused_roi_feats(self.mask_roi_extractor[-1], x, rois, semantic_feat, 'mask')
         probs, last = [], None
-        for i in range(self.num_stages):
-            head = self.mask_head[i]
+        for head in self.mask_head:
             last = head.res_features(mask_feats, last) if self.mask_info_flow \
                 else head.conv_features(mask_feats)
-            probs.append(head.get_mask_probs(head.upsample_features(last), det_labels))
-        return sum(probs) / float(len(probs))
+            probs.append(head.get_mask_probs(head.upsample_features(last), labels))
+        return probs
 
-    def aug_test(self, imgs, img_metas, proposals=None, rescale=False, segm=None):
-        """htc.py:441-561 with ``keep_all_stages=False``: each view's semantic feature and stage loop, merged boxes
-        and scores, then the mask ensemble of every stage on every view (``mask_roi_extractor[-1]`` + semantic
-        fusion, mask information flow) merged over the A x stages entries, ordered by view and then by stage ->
-        ``(bbox_results, probs [k, 28, 28])``.  ``rescale`` is ignored: the boxes are in the original image scale
-        (htc.py:506).  ``proposals``: merged ``[(props, valid)]`` in the original scale instead of the RPN.
-        ``segm='rle'``: ``(bbox_results, segm_results)`` (htc.py:550-558)."""
-        from .post_processing import bbox2result
-        want_rle = self._check_segm(segm)
-        det_bboxes, det_labels, masks = self.aug_test_dets(imgs, img_metas, proposals)
-        if want_rle:
-            masks = self._aug_segms(self.mask_head[-1], masks, det_bboxes, det_labels, img_metas)
-        return bbox2result(det_bboxes, det_labels, self.bbox_head[-1].num_classes), masks
-
-    def aug_test_dets(self, imgs, img_metas, proposals=None):
-        """-> ``(det_bboxes [k,5], det_labels [k], mask_probs [k,28,28])`` device tensors, original image scale."""
-        from . import functional as BF
-        from .merge_augs import merge_aug_masks
-        if self.test_cfg.get('keep_all_stages', False):
-            raise NotImplementedError('keep_all_stages=True (per-stage results) is not built')
-        self._check_aug(img_metas)
-        feats = self.extract_feats(imgs)
-        semantic_feats = [self.semantic_head(x)[1] if self.with_semantic else None for x in feats]
-        det_bboxes, det_labels = self._aug_test_dets(feats, img_metas, proposals, semantic_feats)
-        if det_bboxes.shape[0] == 0:
-            return det_bboxes, det_labels, det_bboxes.new_zeros((0, 28, 28))
-        rois_all = BF.aug_map_boxes([det_bboxes[:, :4]] * len(feats), self._view_geoms(img_metas), back=False,
-                                    mode='rois')
-        probs, entry_metas = [], []
-        ext = self.mask_roi_extractor[-1]
-        for a, (x, meta) in enumerate(zip(feats, img_metas)):
-            mask_feats = self._fused_roi_feats(ext, x, rois_all[a], semantic_feats[a], 'mask')
-            last = None
-            for i in range(self.num_stages):
-                head = self.mask_head[i]
-                last = head.res_features(mask_feats, last) if self.mask_info_flow \
-                    else head.conv_features(mask_feats)
-                probs.append(head.get_mask_probs(head.upsample_features(last), det_labels))
-                entry_metas.append(meta)
-        return det_bboxes, det_labels, merge_aug_masks(probs, entry_metas, self.test_cfg.rcnn)
+    def _ensemble_masks(self, x, mask_rois, det_labels, semantic_feat):
+        """The mean of the per-stage probabilities (``merge_aug_masks`` without weights)."""
+        return self._mask_probs(x, semantic_feat, mask_rois, det_labels)
 
 
 @DETECTORS.register_module

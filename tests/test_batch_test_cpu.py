@@ -139,6 +139,19 @@ def test_the_four_detector_classes_have_the_entry_point():
         assert callable(getattr(cls, 'simple_test_batch'))
 
 
+def test_the_test_time_flows_are_written_once():
+    """the cascades inherit ``TwoStageDetector``'s flows and their device-tensor cores; they supply hooks only"""
+    for cls in (detectors.CascadeRCNN, detectors.HybridTaskCascade):
+        for name in ('simple_test', 'simple_test_batch', 'simple_test_dets', 'aug_test_dets', '_stage_loop'):
+            assert name not in vars(cls), (cls.__name__, name)
+
+
+def test_the_four_detector_classes_expose_the_device_tensor_cores():
+    for cls in (detectors.FasterRCNN, detectors.MaskRCNN, detectors.CascadeRCNN, detectors.HybridTaskCascade):
+        for name in ('simple_test_dets', 'aug_test_dets'):
+            assert getattr(cls, name) is getattr(detectors.TwoStageDetector, name)
+
+
 def _cpu_model(which):
     tmp = tempfile.mkdtemp(prefix='bgs_batch_cpu_')
     return bgs.build_detector(to_config_dict(GA._configs(tmp, which)), train_cfg=None,

@@ -218,8 +218,6 @@ def test_aug_test_vs_executed_reference(which, monkeypatch):
             db, dl = model.aug_test_bboxes(feats, metas, plist, model.test_cfg.rcnn)
             if which == 'mask':
                 probs = model.aug_test_mask(feats, metas, db, dl)
-        elif which == 'cascade':
-            db, dl = model._aug_test_dets(feats, metas, plist, [None] * len(feats))
         else:
             db, dl, probs = model.aug_test_dets(imgs, metas, proposals=plist)
     assert np.abs(seen['scores'][::4, ::7].cpu().numpy() - z['%s/merged_scores' % which]).max() < 2e-5

@@ -428,6 +428,36 @@ def test_different_images_and_shapes(which, monkeypatch):
             np.testing.assert_allclose(got[b][1].cpu().numpy(), exp_m.cpu().numpy(), rtol=1e-4, atol=1e-5)
 
 
+def _assert_core_is_entry_point(core, res, with_mask):
+    """``(det_bboxes, det_labels, probs | None)`` of a ``*_test_dets`` core against the entry point's return"""
+    db, dl, probs = core
+    boxes = _boxes_of(res)
+    assert sum(r.shape[0] for r in boxes) > 0
+    exp = PP.bbox2result(db, dl, len(boxes) + 1)
+    assert len(exp) == len(boxes) and all(np.array_equal(p, q) for p, q in zip(exp, boxes))
+    if with_mask:
+        assert isinstance(res, tuple) and probs.shape == (db.shape[0], 28, 28) and torch.equal(probs, res[1])
+    else:
+        assert probs is None and not isinstance(res, tuple)
+
+
+@pytest.mark.parametrize('which', WHICH)
+def test_device_tensor_cores_equal_the_entry_points(which):
+    """``simple_test_dets`` / ``aug_test_dets`` (the shared cores) + ``bbox2result`` are ``simple_test`` /
+    ``aug_test(rescale=True)`` array for array; the mask probabilities bit for bit"""
+    model = _model(which)
+    with_mask = which in ('mask', 'htc')
+    img, meta = _images(1), _meta(scale=0.8)
+    with torch.no_grad():
+        for rescale in (False, True):
+            core = model.simple_test_dets(img, [meta], proposals=None, rescale=rescale)
+            _assert_core_is_entry_point(core, model.simple_test(img, [meta], rescale=rescale), with_mask)
+        imgs, metas = GA.views()
+        imgs = [i.to(DEV) for i in imgs]
+        core = model.aug_test_dets(imgs, metas, proposals=None)
+        _assert_core_is_entry_point(core, model.aug_test(imgs, metas, rescale=True), with_mask)
+
+
 def test_simple_test_on_a_batch_tensor_is_unchanged():
     """the old entry point still takes a [B > 1, ...] tensor with one meta and answers in the one-image form; the
     trap is closed by the new entry point"""
