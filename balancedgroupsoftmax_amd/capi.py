@@ -197,6 +197,11 @@ SIGNATURES = {
                                           ctypes.c_longlong, c_ptr, c_ptr, c_ptr]),
     'bgs_rle_to_string': (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int, c_ptr, ctypes.c_longlong, c_ptr]),
     'bgs_rle_from_string': (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int, c_ptr, ctypes.c_longlong, c_ptr]),
+    'bgs_lvis_box_iou': (ctypes.c_int, [c_ptr] * 5 + [ctypes.c_int] + [ctypes.c_longlong] * 3 + [c_ptr, c_ptr]),
+    'bgs_lvis_rle_iou': (ctypes.c_int, [c_ptr] * 7 + [ctypes.c_int] + [ctypes.c_longlong] * 3 + [c_ptr, c_ptr]),
+    'bgs_lvis_match_workspace_bytes': (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]),
+    'bgs_lvis_match': (ctypes.c_int, [c_ptr] * 4 + [ctypes.c_int] + [ctypes.c_longlong] * 2 + [c_ptr] * 4
+                       + [c_ptr, ctypes.c_int, c_ptr, ctypes.c_int, c_ptr, ctypes.c_size_t] + [c_ptr] * 4 + [c_ptr]),
     'bgs_mask_gt_logits': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_ptr, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, c_f32p, c_ptr]),
     'bgs_mask_bce_partials': (ctypes.c_int, [ctypes.c_int]),

@@ -2548,6 +2548,150 @@ def mask_rle(probs, boxes, scale_factor, thr, img_hw):
     return [{'size': sizes[k], 'counts': strings[k]} for k in range(len(strings))]
 
 
+# ----------------------------------------------------------------------------------------
+# LVIS evaluation  (lvis-api/lvis/eval.py:116-292; csrc/lvis_eval.hip)
+# ----------------------------------------------------------------------------------------
+class LvisProblems(object):
+    """The CSR description of the (image, category) problems of an evaluation, validated once on the host and uploaded
+    once: ``dt_off`` / ``gt_off`` / ``iou_off`` int64 ``[P + 1]`` as host numpy (``.dt_off`` ...) and as device tensors
+    (``.dt_off_d`` ...); ``P``, ``ND``, ``NG`` and ``total`` (the number of IoU entries)."""
+
+    def __init__(self, dt_off, gt_off, device):
+        import numpy as np
+        dt_off = np.ascontiguousarray(dt_off, dtype=np.int64).reshape(-1)
+        gt_off = np.ascontiguousarray(gt_off, dtype=np.int64).reshape(-1)
+        if dt_off.shape != gt_off.shape or dt_off.size < 1:
+            raise ValueError('lvis problems: dt_off and gt_off must both be [P + 1]')
+        for o in (dt_off, gt_off):
+            if o[0] != 0 or (np.diff(o) < 0).any():
+                raise ValueError('lvis problems: offsets must start at 0 and never decrease')
+        self.P = int(dt_off.size) - 1
+        self.ND, self.NG = int(dt_off[-1]), int(gt_off[-1])
+        self.dt_off, self.gt_off = dt_off, gt_off
+        self.iou_off = np.zeros(self.P + 1, dtype=np.int64)
+        np.cumsum(np.diff(dt_off) * np.diff(gt_off), out=self.iou_off[1:])
+        self.total = int(self.iou_off[-1])
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('balancedgroupsoftmax_amd ops run only on the GPU (hand-written HIP kernels); '
+                               'got device %s. There is no CPU fallback.' % self.device)
+        table = torch.from_numpy(np.stack([dt_off, gt_off, self.iou_off])).to(self.device)      # one upload
+        self.dt_off_d, self.gt_off_d, self.iou_off_d = table[0], table[1], table[2]
+
+
+def _f64c(t, shape_tail, n, what):
+    t = t.detach().to(torch.float64).contiguous()
+    if tuple(t.shape) != (n,) + shape_tail:
+        raise ValueError('%s: expected shape %r, got %r' % (what, (n,) + shape_tail, tuple(t.shape)))
+    return t
+
+
+def lvis_box_iou(dt_boxes, gt_boxes, problems):
+    """``mask_utils.iou(dt, gt, iscrowd=0)`` of ``LVISEval.compute_iou`` (eval.py:168-192) over ``[x, y, w, h]`` boxes
+    for every problem in one launch (``bgs_lvis_box_iou``): ``dt_boxes [ND, 4]`` (score order inside a problem),
+    ``gt_boxes [NG, 4]``, ``problems`` a :class:`LvisProblems` -> fp64 ``[total]``: problem ``p``'s row-major
+    ``[D_p, G_p]`` matrix begins at ``problems.iou_off[p]``.  fp64, one rounding per operation, as ``bbIou``."""
+    _require_cuda(dt_boxes, gt_boxes)
+    lib = capi.load()
+    pr = problems
+    dt = _f64c(dt_boxes, (4,), pr.ND, 'lvis_box_iou dt_boxes')
+    gt = _f64c(gt_boxes, (4,), pr.NG, 'lvis_box_iou gt_boxes')
+    out = torch.empty(pr.total, dtype=torch.float64, device=pr.device)
+    rc = lib.bgs_lvis_box_iou(capi.ptr(dt), capi.ptr(gt), capi.ptr(pr.dt_off_d), capi.ptr(pr.gt_off_d),
+                              capi.ptr(pr.iou_off_d), pr.P, pr.ND, pr.NG, pr.total, capi.ptr(out),
+                              capi.current_stream(pr.device))
+    capi.check('bgs_lvis_box_iou', rc)
+    return out
+
+
+def _rle_table(counts, offsets, sizes, n, what):
+    import numpy as np
+    if torch.is_tensor(counts):
+        _require_cuda(counts)
+        raise TypeError('%s: run lengths are host arrays (what mask_rle_counts returns)' % what)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64).reshape(-1, 2)
+    if offsets.size != n + 1 or sizes.shape[0] != n:
+        raise ValueError('%s: expected %d masks, got offsets %r and sizes %r' % (what, n, offsets.shape, sizes.shape))
+    if offsets[0] != 0 or (np.diff(offsets) < 0).any() or offsets[-1] > counts.size:
+        raise ValueError('%s: offsets must start at 0, never decrease and end inside the counts' % what)
+    return counts, offsets, sizes
+
+
+def lvis_rle_iou(dt_rles, gt_rles, problems):
+    """The same matrices for masks given as run lengths (``rleIou`` with ``iscrowd = 0``; ``bgs_lvis_rle_iou``).
+    ``dt_rles`` / ``gt_rles``: ``(counts uint32 [total], offsets int64 [K + 1], sizes [K, 2])`` host arrays, the triple
+    :func:`mask_rle_counts` returns.  Both masks of a pair must have the same size (checked here, per problem).
+    One lane walks the two run lists of a pair in step; no dense mask is built."""
+    import numpy as np
+    lib = capi.load()
+    pr = problems
+    dc, do, ds = _rle_table(*dt_rles, pr.ND, 'lvis_rle_iou dt_rles')
+    gc, go, gs = _rle_table(*gt_rles, pr.NG, 'lvis_rle_iou gt_rles')
+    nd, ng = np.diff(pr.dt_off), np.diff(pr.gt_off)
+    both = np.nonzero((nd > 0) & (ng > 0))[0]
+    if both.size:
+        # every mask of a problem against the size of the problem's first ground truth
+        ref = np.zeros((pr.P, 2), np.int64)
+        ref[both] = gs[pr.gt_off[both]]
+        has = np.zeros(pr.P, bool)
+        has[both] = True
+        for sizes, n in ((ds, nd), (gs, ng)):
+            owner = np.repeat(np.arange(pr.P), n)
+            bad = has[owner] & (sizes != ref[owner]).any(axis=1)
+            if bad.any():
+                raise ValueError('lvis_rle_iou: masks of different sizes in problem %d' % int(owner[np.argmax(bad)]))
+    dev = pr.device
+    dc_d = torch.from_numpy(dc.view(np.int32)).to(dev)
+    gc_d = torch.from_numpy(gc.view(np.int32)).to(dev)
+    do_d, go_d = torch.from_numpy(do).to(dev), torch.from_numpy(go).to(dev)
+    out = torch.empty(pr.total, dtype=torch.float64, device=dev)
+    rc = lib.bgs_lvis_rle_iou(capi.ptr(dc_d), capi.ptr(do_d), capi.ptr(gc_d), capi.ptr(go_d), capi.ptr(pr.dt_off_d),
+                              capi.ptr(pr.gt_off_d), capi.ptr(pr.iou_off_d), pr.P, pr.ND, pr.NG, pr.total,
+                              capi.ptr(out), capi.current_stream(dev))
+    capi.check('bgs_lvis_rle_iou', rc)
+    return out
+
+
+def lvis_match(ious, problems, dt_area, gt_area, gt_ignore, not_exhaustive, area_rng, iou_thrs, tables=True):
+    """The greedy matching of ``LVISEval.evaluate_img`` (eval.py:194-292) for every problem, area range and threshold
+    in one launch (``bgs_lvis_match``).  ``ious`` fp64 ``[total]`` (:func:`lvis_box_iou` / :func:`lvis_rle_iou`),
+    ``dt_area [ND]`` / ``gt_area [NG]`` fp64, ``gt_ignore [NG]`` and ``not_exhaustive [P]`` bool / uint8 device
+    tensors; ``area_rng`` ``[A, 2]`` and ``iou_thrs`` ``[T]`` host float64 values (A <= 4, T <= 16).
+    Returns ``(dt_match int32 [ND, A, T], dt_ignore uint8 [ND, A, T], dt_bits int32 [A, ND], gt_ignore uint8
+    [A, NG])``: ``dt_match`` is the ground truth's index inside its problem or -1; ``dt_bits`` packs bit ``t`` =
+    matched and bit ``16 + t`` = ignored.  ``tables=False`` skips the two full tables (they are None)."""
+    import numpy as np
+    _require_cuda(ious, dt_area, gt_area, gt_ignore, not_exhaustive)
+    lib = capi.load()
+    pr = problems
+    dev = pr.device
+    rng = np.ascontiguousarray(area_rng, dtype=np.float64).reshape(-1, 2)
+    thr = np.ascontiguousarray(iou_thrs, dtype=np.float64).reshape(-1)
+    A, T = int(rng.shape[0]), int(thr.shape[0])
+    ious = _f64c(ious, (), pr.total, 'lvis_match ious')
+    dt_area = _f64c(dt_area, (), pr.ND, 'lvis_match dt_area')
+    gt_area = _f64c(gt_area, (), pr.NG, 'lvis_match gt_area')
+    gt_ignore = gt_ignore.to(torch.uint8).contiguous()
+    nel = not_exhaustive.to(torch.uint8).contiguous()
+    if gt_ignore.numel() != pr.NG or nel.numel() != pr.P:
+        raise ValueError('lvis_match: gt_ignore must be [NG] and not_exhaustive [P]')
+    dt_match = torch.empty((pr.ND, A, T), dtype=torch.int32, device=dev) if tables else None
+    dt_ig = torch.empty((pr.ND, A, T), dtype=torch.uint8, device=dev) if tables else None
+    dt_bits = torch.empty((A, pr.ND), dtype=torch.int32, device=dev)
+    gt_ig = torch.empty((A, pr.NG), dtype=torch.uint8, device=dev)
+    ws_bytes = int(lib.bgs_lvis_match_workspace_bytes(pr.NG, A, T))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    rc = lib.bgs_lvis_match(capi.ptr(ious), capi.ptr(pr.dt_off_d), capi.ptr(pr.gt_off_d), capi.ptr(pr.iou_off_d),
+                            pr.P, pr.ND, pr.NG, capi.ptr(dt_area), capi.ptr(gt_area), capi.ptr(gt_ignore),
+                            capi.ptr(nel), rng.ctypes.data_as(ctypes.c_void_p), A,
+                            thr.ctypes.data_as(ctypes.c_void_p), T, capi.ptr(ws), ws_bytes, capi.ptr(dt_match),
+                            capi.ptr(dt_ig), capi.ptr(dt_bits), capi.ptr(gt_ig), capi.current_stream(dev))
+    capi.check('bgs_lvis_match', rc)
+    return dt_match, dt_ig, dt_bits, gt_ig
+
+
 def mask_gt_logits(feat, weight, bias, labels):
     """``feat [P, pixels, C]``, ``weight [K, C]``, ``labels [P]`` -> ``[P, pixels]`` logits of each
     RoI's own class channel (no gradient: test-time / inspection path)."""

@@ -880,6 +880,51 @@ int bgs_mask_bce(const float* feat, const float* weight, const float* bias, cons
                  int C, int num_classes, float* partial_out, float* dfeat, float* dweight,
                  float* dbias, bgs_stream_t stream);
 
+/* LVIS evaluation (csrc/lvis_eval.hip): what tools/test_lvis.py reaches through lvis_eval -> LVISEval.evaluate
+ * (lvis-api/lvis/eval.py:116-292), for every (image, category) PROBLEM of an evaluation in one launch per kernel.
+ * Problem p owns detections dt_off[p] .. dt_off[p + 1] (already in descending score order), ground truths
+ * gt_off[p] .. gt_off[p + 1] (annotation order) and the row-major [D_p, G_p] fp64 block of `ious` that begins at
+ * iou_off[p]; dt_off / gt_off / iou_off are device int64 [P + 1], non-decreasing, iou_off[p + 1] - iou_off[p] =
+ * D_p * G_p, iou_off[P] = total, dt_off[P] <= ND, gt_off[P] <= NG (the caller's guarantee; a problem whose offsets
+ * leave [0, ND] / [0, NG] is skipped).  P == 0 is BGS_OK.
+ * bgs_lvis_box_iou: mask_utils.iou of eval.py:191 for iou_type 'bbox' = bbIou of pycocotools' maskApi.c with
+ *   iscrowd = 0.  dt_boxes [ND, 4] / gt_boxes [NG, 4] fp64 [x, y, w, h].  da = dw * dh; ga = gw * gh;
+ *   w = min(dx + dw, gx + gw) - max(dx, gx); h likewise; 0 when w <= 0 or h <= 0, else i = w * h, u = da + ga - i,
+ *   o = i / u: each a single correctly rounded fp64 operation (no fused multiply-add).
+ * bgs_lvis_rle_iou: the same call for iou_type 'segm' = rleIou with iscrowd = 0.  dt_counts / gt_counts: uint32 run
+ *   lengths, mask k's runs are counts[rle_off[k] : rle_off[k + 1]] (dt_rle_off [ND + 1], gt_rle_off [NG + 1] device
+ *   int64; the layout bgs_mask_rle_write produces).  Intersection and union are 64-bit pixel counts, o = double(i) /
+ *   double(u), 0 when u == 0.  Both masks of a pair must have the same size (the caller checks); no dense mask is
+ *   built.
+ * bgs_lvis_match: the greedy matching of LVISEval.evaluate_img (eval.py:194-292) for A area ranges (host_area_rng
+ *   [A, 2] fp64, HOST, bounds inclusive) and T IoU thresholds (host_iou_thrs [T] fp64, HOST) at once; A <= 4 and
+ *   T <= 16, BGS_ERR_UNSUPPORTED beyond.  dt_area [ND] / gt_area [NG] fp64, gt_ignore [NG] uint8 (the annotation's
+ *   'ignore'), prob_not_exhaustive [P] uint8 (the category is in the image's not_exhaustive_category_ids).  A ground
+ *   truth is ignored for a range when its flag is set or its area lies outside; ground truths are visited non-ignored
+ *   first, then ignored, each group in annotation order; a detection starts at min(thr, 1 - 1e-10), skips matched
+ *   ground truths, stops at the first ignored one when it already holds a non-ignored one, takes a ground truth
+ *   whose IoU is >= the running best (the later of equals wins); the taken ground truth is marked matched (ignored
+ *   ones too) and hands its ignore flag to the detection; an unmatched detection is ignored when its area lies
+ *   outside the range or prob_not_exhaustive is set.
+ *   Outputs (each may be NULL except gt_ignore_out): dt_match [ND, A, T] int32 = the ground truth's index INSIDE the
+ *   problem (annotation order) or -1; dt_ignore [ND, A, T] uint8; dt_bits [A, ND] uint32: bit t = matched at
+ *   threshold t, bit 16 + t = ignored; gt_ignore_out [A, NG] uint8.
+ *   G_p is not capped: problems with more than 64 ground truths keep their matched flags in `workspace`
+ *   (>= bgs_lvis_match_workspace_bytes(NG, A, T), which is 0 when no problem can be that large). */
+int bgs_lvis_box_iou(const double* dt_boxes, const double* gt_boxes, const long long* dt_off, const long long* gt_off,
+                     const long long* iou_off, int P, long long ND, long long NG, long long total, double* ious,
+                     bgs_stream_t stream);
+int bgs_lvis_rle_iou(const unsigned* dt_counts, const long long* dt_rle_off, const unsigned* gt_counts,
+                     const long long* gt_rle_off, const long long* dt_off, const long long* gt_off,
+                     const long long* iou_off, int P, long long ND, long long NG, long long total, double* ious,
+                     bgs_stream_t stream);
+size_t bgs_lvis_match_workspace_bytes(long long NG, int A, int T);
+int bgs_lvis_match(const double* ious, const long long* dt_off, const long long* gt_off, const long long* iou_off,
+                   int P, long long ND, long long NG, const double* dt_area, const double* gt_area,
+                   const uint8_t* gt_ignore, const uint8_t* prob_not_exhaustive, const double* host_area_rng, int A,
+                   const double* host_iou_thrs, int T, void* workspace, size_t workspace_bytes, int* dt_match,
+                   uint8_t* dt_ignore, unsigned* dt_bits, uint8_t* gt_ignore_out, bgs_stream_t stream);
+
 /* Gradient clipping + SGD update of ALL trainable tensors (csrc/optim.hip): the reference's optimizer hook
  * `DistOptimizerHook.after_train_iter` (mmdet/core/utils/dist_utils.py:51-58): `clip_grads` (max_norm = 35, L2:
  * torch.nn.utils.clip_grad_norm_) -> `optimizer.step()` (torch.optim.SGD with momentum and weight decay,
