@@ -5,10 +5,12 @@ from PyTorch-ROCm through the reference's own registry keys and config schema.
 """
 from . import (backbone, bbox_heads, checkpoint, config, detectors, gs_tables, losses, lvis_eval,  # noqa: F401
                mask_heads, roi_extractor, rpn, semantic_head, train)  # (imports populate the registries)
+from .apis import inference_detector, init_detector
 from .builder import (build_backbone, build_detector, build_head, build_loss, build_neck,
                       build_roi_extractor, build_shared_head)
 from .config import Config, ConfigDict
 from .lvis_eval import LVISEval, LVISGroundTruth, results2json
+from .pipelines import TestPipeline, rescale_size
 from .registry import (BACKBONES, DETECTORS, HEADS, LOSSES, NECKS, ROI_EXTRACTORS, SHARED_HEADS,
                        Registry, build_from_cfg)
 
@@ -17,4 +19,5 @@ __version__ = '0.1.0'
 __all__ = ['BACKBONES', 'DETECTORS', 'HEADS', 'LOSSES', 'NECKS', 'ROI_EXTRACTORS',
            'SHARED_HEADS', 'Registry', 'build_from_cfg', 'build_backbone', 'build_detector',
            'build_head', 'build_loss', 'build_neck', 'build_roi_extractor', 'build_shared_head',
-           'Config', 'ConfigDict', 'LVISEval', 'LVISGroundTruth', 'lvis_eval', 'results2json']
+           'Config', 'ConfigDict', 'LVISEval', 'LVISGroundTruth', 'lvis_eval', 'results2json',
+           'TestPipeline', 'inference_detector', 'init_detector', 'rescale_size']

@@ -669,6 +669,26 @@ int bgs_aug_merge_masks(const float* const* host_masks, const int* host_flip, in
                         bgs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Test-time image pipeline: V uint8 HWC (BGR, as mmcv.imread gives) sources -> out [V, 3, Hp, Wp] float32, every
+ *   element written, in one launch per 16 views.  Replaces Resize(keep_ratio=True) -> RandomFlip -> Normalize ->
+ *   Pad -> ImageToTensor of mmdet/datasets/pipelines/transforms.py:111-124, 201-215, 243-252, 291-296 (and the zero
+ *   padding of batch collation).
+ *   host_src [V] device pointers; host_geom [V][6] HOST ints (h, w, row stride in bytes >= 3 * w, new_h, new_w,
+ *     flip), passed to the kernel by value: no allocation, no upload, no synchronisation.
+ *   Inside (y < new_h, x < new_w): the resized image's column is new_w - 1 - x where flip; its uint8 value is
+ *     OpenCV's fixed-point INTER_LINEAR (coordinates in double, coefficients rint(c * 2048) as short,
+ *     (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2; an unchanged size is a copy), computed in
+ *     the kernel; out plane p = lut[p][value of source channel (swap_rb ? 2 - p : p)], lut [3][256] float32 on the
+ *     device (the host builds it: (float32(u) - mean[p]) / std[p]).  Outside: 0.0f.
+ *   Any Wp (16-byte stores where Wp % 4 == 0 and out is 16-byte aligned).  An exact 2x reduction is NOT turned
+ *     into INTER_AREA as cv2 does.
+ *   channels != 3: BGS_ERR_UNSUPPORTED; a null pointer, a non-positive size, stride < 3 * w, new_h > Hp or
+ *     new_w > Wp: BGS_ERR_INVALID_ARG (all before anything is launched).
+ * ---------------------------------------------------------------------------------- */
+int bgs_img_prep_u8(const unsigned char* const* host_src, const int* host_geom, int V, int channels,
+                    const float* lut, int swap_rb, float* out, int Hp, int Wp, bgs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Target assignment without the [G, A] IoU matrix.  Replaces MaxIoUAssigner.assign /
  *   assign_wrt_overlaps (mmdet/core/bbox/assigners/max_iou_assigner.py:47-180, incl. its CPU
  *   fallback for > 50 GTs and the Python loop over GTs) and bbox_overlaps
