@@ -232,6 +232,9 @@ SIGNATURES = {
     'bgs_aug_merge_masks': (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p, c_ptr]),
     'bgs_img_prep_u8': (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int, ctypes.c_int, c_f32p, ctypes.c_int, c_f32p,
                                        ctypes.c_int, ctypes.c_int, c_ptr]),
+    'bgs_gt_mask_prep_u8': (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int, c_ptr, c_ptr, ctypes.c_longlong, c_ptr,
+                                           ctypes.c_int, ctypes.c_int, c_ptr]),
+    'bgs_gt_seg_prep_u8': (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int, c_ptr, ctypes.c_int, ctypes.c_int, c_ptr]),
     'bgs_iou_assign_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 3),
     'bgs_iou_assign': (ctypes.c_int, [c_f32p, ctypes.c_longlong, ctypes.c_int, c_ptr, c_f32p, c_ptr,
                                       ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,

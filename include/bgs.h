@@ -689,6 +689,41 @@ int bgs_img_prep_u8(const unsigned char* const* host_src, const int* host_geom, 
                     const float* lut, int swap_rb, float* out, int Hp, int Wp, bgs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Training-time ground truth (csrc/gt_prep.hip): the gt masks and semantic maps of a batch at the padded network
+ *   size, one launch each.  Replaces, for them, Resize(keep_ratio=True) -> RandomFlip -> Pad ->
+ *   SegResizeFlipPadRescale of mmdet/datasets/pipelines/transforms.py:134-150, 212-214, 254-261, 386-405 (masks:
+ *   mmcv.imrescale(mask, scale_factor, interpolation='nearest'), mask[:, ::-1], mmcv.impad with 0) and the zero
+ *   padding of batch collation.
+ *   A descriptor is 12 ints: flags (bit 0: the source is RLE, bit 1: flip), h, w (source), new_h, new_w (resized),
+ *     nruns, src (64 bit, low word first: the device address of a dense uint8 [h, w] source, or the index of the
+ *     mask's first entry in prefix), pad_h, pad_w, hs, ws (semantic maps only; 0 for masks).  host_desc is the
+ *     HOST copy every check reads, desc the same table on the DEVICE, which the kernel reads: no allocation, no
+ *     upload, no synchronisation here.
+ *   The nearest rule is OpenCV's INTER_NEAREST in double precision: along an axis resized from m to n,
+ *     s = min((int)floor(d * (1.0 / ((double)n / m))), m - 1); an unchanged size is a copy.
+ * bgs_gt_mask_prep_u8: out [M, Hp, Wp] uint8, every byte written.  For y < new_h, x < new_w mask m's value is the
+ *     source pixel (sy, sx) of the resized pixel (y, flip ? new_w - 1 - x : x); 0 elsewhere (Pad and the batch
+ *     padding).  An RLE source is never expanded: prefix [prefix_len] uint32 holds, per mask, the inclusive prefix
+ *     sums of its COCO run lengths (host_prefix: the host copy); the value is the parity of the run that holds the
+ *     column-major index sx * h + sy, found by bisection.  Zero-length runs are allowed.
+ * bgs_gt_seg_prep_u8: out [N, Hs, Ws] uint8, every byte written.  For ys < hs, xs < ws (hs = int(pad_h * f + 0.5)
+ *     for the configured factor f, ws likewise; the host computes them) the value is position (yp, xp) of the map
+ *     padded to [pad_h, pad_w], by the nearest rule from (pad_h, pad_w) to (hs, ws): 0 where yp >= new_h or
+ *     xp >= new_w (the reference pads the map with 0, transforms.py:399-400), the flipped, resized source as above
+ *     otherwise.  hs == pad_h and ws == pad_w (factor 1) is the padded map itself.  0 beyond hs, ws.  Dense
+ *     sources only (an RLE flag: BGS_ERR_UNSUPPORTED).
+ *   Any output width (16-byte stores where it is a multiple of 16 and out is 16-byte aligned).
+ *   A null pointer, a non-positive size, new_h > Hp / pad_h, new_w > Wp / pad_w, hs > Hs, ws > Ws, runs outside
+ *     prefix, or run lengths that do not sum to h * w: BGS_ERR_INVALID_ARG; h * w > 2^31 - 1: BGS_ERR_UNSUPPORTED
+ *     (all before anything is launched).  M == 0 / N == 0 is BGS_OK.
+ * ---------------------------------------------------------------------------------- */
+int bgs_gt_mask_prep_u8(const int* host_desc, const int* desc, int M, const unsigned* host_prefix,
+                        const unsigned* prefix, long long prefix_len, unsigned char* out, int Hp, int Wp,
+                        bgs_stream_t stream);
+int bgs_gt_seg_prep_u8(const int* host_desc, const int* desc, int N, unsigned char* out, int Hs, int Ws,
+                       bgs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Target assignment without the [G, A] IoU matrix.  Replaces MaxIoUAssigner.assign /
  *   assign_wrt_overlaps (mmdet/core/bbox/assigners/max_iou_assigner.py:47-180, incl. its CPU
  *   fallback for > 50 GTs and the Python loop over GTs) and bbox_overlaps
