@@ -122,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void gs_loss_rowwave_kernel(
         const float zt = seg[tgt];  // target logit, read before the in-place exp
         float m, S;
         bgs::bin_softmax_inplace(seg, n, lane, m, S);
-        term = coef * ((m + logf(S)) - zt);
+        term = coef * (logf(S) - (zt - m));
         if (WRITE_GRAD) bgs::bin_grad_inplace(seg, n, lane, coef / S, coef, tgt);
       }
       if (lane == b) lacc += term;
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void gs_loss_generic_kernel(
       float ps = 0.f;
       for (int j = tid; j < n; j += kBlock) ps += __expf(zr[s + j] - m);
       const float S = block_sum(ps, sm);
-      if (tid == 0) acc[b] += coef * ((m + logf(S)) - zr[s + bl]);
+      if (tid == 0) acc[b] += coef * (logf(S) - (zr[s + bl] - m));
       if (WRITE_GRAD) {
         const float invS = 1.f / S;
         for (int j = tid; j < n; j += kBlock)
@@ -788,7 +788,7 @@ __global__ __launch_bounds__(kBlock) void gs_head_fused_kernel(GsHeadArgs a) {
         const float zt = seg[tgt];
         float m, S;
         bgs::bin_softmax_inplace(seg, n, lane, m, S);
-        term = coef * ((m + logf(S)) - zt);
+        term = coef * (logf(S) - (zt - m));
         if (WRITE_GRAD) bgs::bin_grad_inplace(seg, n, lane, coef / S, coef, tgt);
       }
       if (lane == b) lacc += term;
@@ -956,7 +956,7 @@ __device__ __forceinline__ float gs_bin_loss_direct(const float* __restrict__ se
     const int j = lane + BGS_WAVE * u;
     if (ok[u]) gseg[j] = x[u] * k - (j == tgt ? coef : 0.f);
   }
-  return coef * ((m + logf(S)) - zt);
+  return coef * (logf(S) - (zt - m));
 }
 
 template <int VEC, bool WRITE_GRAD, bool BOX, int RPAR, bool DIRECT>
@@ -1169,7 +1169,7 @@ __global__ __launch_bounds__(kBlock * RPAR, 6) void gs_head_multi_kernel(GsHeadA
         const float zt = seg[tgt];
         float m, S;
         bgs::bin_softmax_inplace(seg, n, lane, m, S);
-        term = coef * ((m + logf(S)) - zt);
+        term = coef * (logf(S) - (zt - m));
         if (WRITE_GRAD) {
           bgs::bin_grad_inplace(seg, n, lane, coef / S, coef, tgt);
           if (DIRECT)        // the wave's own LDS writes, read back in order: no barrier

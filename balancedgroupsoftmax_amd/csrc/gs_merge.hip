@@ -8,6 +8,11 @@
 //     scores[r, 0] = p_0[r, 0]
 //     scores[r, c] = p_0[r, 1] * p_b[r, k]     with column cls2col[c] = s_b + k,  k >= 1
 // ("others" column 0 of every foreground bin is dropped; rows do not sum to 1.)
+// The rule is by CLASS, as in the reference (merge[:, 0] = bg_score[:, 0]), on whatever device table arrives: class 0
+// is p_0[r, 0] whatever cls2col[0] holds; a class c >= 1 is p_0[r, 1] * p[r, cls2col[c]] for ANY column in [0, W) (the
+// background column included) and 0 for a column outside [0, W); p_0[r, 1] = 0 when bin 0 has a single column.
+// Both kernels below follow it, so the scores of a RoI are the same bits in every dispatcher mode and batch size
+// (tests/test_gpu_gs_regimes.py: oracle/gs_oracle.py merge_score_by_table).
 // Algorithmic bytes per RoI: W*4 read + C*4 written = 9,868 B (cls2col stays in L2).
 #include <stdlib.h>
 
@@ -75,6 +80,7 @@ __global__ __launch_bounds__(kBlock) void gs_merge_rowwave_kernel(
     }
     __syncthreads();
     const float pfg = fg_col >= 0 ? row[fg_col] : 0.f;
+    const float pbg = row[bg_col];                              // class 0, whatever cls2col[0] says
     float* out = scores + (size_t)r * C;
     if (PF) {
 #pragma unroll
@@ -83,14 +89,16 @@ __global__ __launch_bounds__(kBlock) void gs_merge_rowwave_kernel(
         if (c >= C) break;
         const int col = cols[i];
         float sc = 0.f;
-        if (col >= 0) sc = (col == bg_col) ? row[col] : pfg * row[col];
+        if (c == 0) sc = pbg;
+        else if (col >= 0) sc = pfg * row[col];
         __builtin_nontemporal_store(sc, out + c);
       }
     } else {
       for (int c = tid; c < C; c += kBlock) {
         const int col = cls2col[c];
         float sc = 0.f;
-        if (col >= 0 && col < W) sc = (col == bg_col) ? row[col] : pfg * row[col];
+        if (c == 0) sc = pbg;
+        else if (col >= 0 && col < W) sc = pfg * row[col];
         out[c] = sc;
       }
     }

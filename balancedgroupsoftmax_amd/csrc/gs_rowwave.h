@@ -93,7 +93,10 @@ __device__ __forceinline__ void bin_softmax_inplace(float* __restrict__ seg, int
 // table): the bin is read from LDS ONCE into registers, max / exp / sum / gradient are
 // computed there and the gradient is written back ONCE.  Reads past the end of the bin stay
 // inside the row buffer (the caller pads it by 64*kSweep floats) and are masked out.
-// Returns the row's loss term  coef * (logsumexp - z[tgt]).
+// Returns the row's loss term  coef * (logsumexp - z[tgt]),  formed as  logf(S) - (zt - m)  here and at every other
+// site (gs_loss.hip): zt - m is exact or nearly so (both lie in the bin, m >= zt), so the term carries the error of
+// logf(S) alone and the loss is shift-invariant like the reference's (zt - m) - log(S); (m + logf(S)) - zt would round
+// the sum to half an ulp of m — 3e-5 per row at a common offset of 1000, whatever the loss.
 template <bool WRITE_GRAD>
 __device__ __forceinline__ float bin_loss_registers(float* __restrict__ seg, int n, int lane,
                                                     float coef, int tgt) {
@@ -125,7 +128,7 @@ __device__ __forceinline__ float bin_loss_registers(float* __restrict__ seg, int
       if (ok[u]) seg[j] = x[u] * k - (j == tgt ? coef : 0.f);
     }
   }
-  return coef * ((m + logf(S)) - zt);
+  return coef * (logf(S) - (zt - m));
 }
 
 // seg[j] = seg[j] * k - (j == tgt ? c : 0)   (gradient of one bin, in place)

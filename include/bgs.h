@@ -166,8 +166,13 @@ int bgs_gs_scale_grad(float* dlogits, const int64_t* host_pred_slice, const floa
  *   (gs_bbox_head_with0.py:239-273): softmax inside every bin, then
  *     scores[r,0] = p_0[r,0];  scores[r,c] = p_0[r,1] * p_b[r, k]  for the column
  *     cls2col[c] = s_b + k of class c (k >= 1);  cls2col[c] < 0  => scores[r,c] = 0.
+ *   The rule is by class on whatever table arrives: class 0 is p_0[r,0] whatever cls2col[0]
+ *   holds; a class c >= 1 is p_0[r,1] * p[r, cls2col[c]] for any column in [0, W) and 0 for a
+ *   column outside it; p_0[r,1] = 0 when bin 0 has one column.  The same bits for every N.
  *   logits [N,W] float, host_pred_slice [B,2] int64 (host), cls2col [C] int32,
  *   scores_out [N,C] float.
+ *   BGS_ERR_UNSUPPORTED (nothing written): B > BGS_MAX_BINS, W > 8000, bins that do not tile
+ *   [0, W) in ascending order; BGS_ERR_INVALID_ARG: a bin that leaves the row.
  * ---------------------------------------------------------------------------------- */
 int bgs_gs_merge_score(const float* logits, const int64_t* host_pred_slice,
                        const int32_t* cls2col,

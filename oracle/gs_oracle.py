@@ -179,6 +179,33 @@ def merge_score(logits, pred_slice, fg_splits, num_classes, dtype=np.float64):
     return merge
 
 
+def merge_score_by_table(logits, pred_slice, cls2col, dtype=np.float64):
+    """The contract of ``bgs_gs_merge_score`` stated on the device table it is given (an arbitrary
+    class -> column map, not the ``fg_splits`` it is usually derived from): softmax inside each bin
+    (same statements as :func:`merge_score`); ``scores[:, 0] = p_0[:, 0]`` whatever ``cls2col[0]``
+    holds (``merge[:, 0] = bg_score[:, 0]``, gs_bbox_head_with0.py:270); for ``c >= 1`` with
+    ``0 <= cls2col[c] < W``: ``scores[:, c] = p_fg * p[:, cls2col[c]]`` with ``p_fg = p_0[:, 1]``
+    (0 when bin 0 has a single column); every other class scores 0.
+    """
+    z = np.asarray(logits).astype(dtype)
+    N, W = z.shape
+    p = np.zeros((N, W), dtype=dtype)
+    for s, n in pred_slice:
+        zi = z[:, int(s):int(s) + int(n)]
+        m = zi.max(axis=1, keepdims=True)
+        e = np.exp(zi - m)
+        p[:, int(s):int(s) + int(n)] = e / e.sum(axis=1, keepdims=True)
+    s0, n0 = int(pred_slice[0][0]), int(pred_slice[0][1])
+    p_fg = p[:, s0 + 1:s0 + 2] if n0 > 1 else np.zeros((N, 1), dtype=dtype)
+    col = np.asarray(cls2col, dtype=np.int64).reshape(-1)
+    valid = (col >= 0) & (col < W)
+    valid[0] = False
+    merge = np.zeros((N, col.shape[0]), dtype=dtype)
+    merge[:, valid] = p_fg * p[:, col[valid]]
+    merge[:, 0] = p[:, s0]
+    return merge
+
+
 # ----------------------------------------------------------------------------
 # deterministic synthetic inputs shared by golden generation, tests and bench
 # ----------------------------------------------------------------------------

@@ -67,6 +67,21 @@ def test_merge_score(name):
     np.testing.assert_allclose(ms.sum(1), g.get(name, 'merge_rowsum'), rtol=1e-5)
 
 
+@pytest.mark.parametrize('name', case_names())
+def test_merge_score_by_table_equals_merge_score(name):
+    """The table-driven statement of the merge (what the kernels are given: a class -> column map) is, on every
+    committed table and case, exactly the ``fg_splits`` statement that is pinned to the executed reference."""
+    from balancedgroupsoftmax_amd import gs_tables
+    case, l2b, ps, fg_splits, cls_w, batch = case_setup(name)
+    c2c = gs_tables.class_to_column(l2b, ps).numpy()
+    for scale in (1.0, 2.0):
+        z = batch['logits'] * np.float32(scale)
+        a = gs_oracle.merge_score_by_table(z, ps, c2c)
+        b = gs_oracle.merge_score(z, ps, fg_splits, C)
+        assert a.dtype == np.float64 and a.shape == b.shape
+        np.testing.assert_array_equal(a, b)
+
+
 def test_reference_observed_values_cfg1():
     """Bin widths of the synthetic 5-bin split (SURVEY.md §8d rule; the survey used a different draw: 286/265)."""
     case, l2b, ps, fg_splits, cls_w, batch = case_setup('n512_cfg1')
