@@ -10,6 +10,8 @@ from .builder import (build_backbone, build_detector, build_head, build_loss, bu
                       build_roi_extractor, build_shared_head)
 from .config import Config, ConfigDict
 from .lvis_eval import LVISEval, LVISGroundTruth, results2json
+from .ops import (DeformConv, DeformConvPack, ModulatedDeformConv, ModulatedDeformConvPack, deform_conv,
+                  modulated_deform_conv)
 from .pipelines import TestPipeline, TrainPipeline, rescale_size
 from .registry import (BACKBONES, DETECTORS, HEADS, LOSSES, NECKS, ROI_EXTRACTORS, SHARED_HEADS,
                        Registry, build_from_cfg)
@@ -20,4 +22,6 @@ __all__ = ['BACKBONES', 'DETECTORS', 'HEADS', 'LOSSES', 'NECKS', 'ROI_EXTRACTORS
            'SHARED_HEADS', 'Registry', 'build_from_cfg', 'build_backbone', 'build_detector',
            'build_head', 'build_loss', 'build_neck', 'build_roi_extractor', 'build_shared_head',
            'Config', 'ConfigDict', 'LVISEval', 'LVISGroundTruth', 'lvis_eval', 'results2json',
-           'TestPipeline', 'TrainPipeline', 'inference_detector', 'init_detector', 'rescale_size']
+           'TestPipeline', 'TrainPipeline', 'inference_detector', 'init_detector', 'rescale_size',
+           'DeformConv', 'DeformConvPack', 'ModulatedDeformConv', 'ModulatedDeformConvPack', 'deform_conv',
+           'modulated_deform_conv']

@@ -32,6 +32,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as BF
+from .ops import OFFSET_PITCH, DeformConv
 from .registry import BACKBONES, NECKS
 
 
@@ -48,13 +49,14 @@ def _fold_conv_bn(conv, bn, pad_cin_to=None):
     CPU tensors (module construction / state-dict tests: the product never computes there) take the
     tensor-op form of the same formula."""
     w = conv.weight
+    cbias = getattr(conv, 'bias', None)      # (ops.DeformConv has no bias attribute, like the reference's)
     if w.is_cuda:
         ctx = contextlib.nullcontext() if _trainable(conv, bn) else torch.no_grad()
         with ctx:
             if bn is not None:
-                return BF.fold_conv_bn(w, conv.bias, bn.weight, bn.bias, bn.running_mean,
+                return BF.fold_conv_bn(w, cbias, bn.weight, bn.bias, bn.running_mean,
                                        bn.running_var, bn.eps, cin_padded=pad_cin_to)
-            return BF.fold_conv_bn(w, conv.bias, cin_padded=pad_cin_to)
+            return BF.fold_conv_bn(w, cbias, cin_padded=pad_cin_to)
     ctx = contextlib.nullcontext() if _trainable(conv, bn) else torch.no_grad()
     with ctx:
         w = conv.weight.float()
@@ -63,9 +65,9 @@ def _fold_conv_bn(conv, bn, pad_cin_to=None):
             scale = bn.weight.float() / torch.sqrt(bn.running_var.float() + bn.eps)
             shift = bn.bias.float() - bn.running_mean.float() * scale
             w = w * scale.view(-1, 1, 1, 1)
-            b = shift if conv.bias is None else shift + conv.bias.float() * scale
+            b = shift if cbias is None else shift + cbias.float() * scale
         else:
-            b = conv.bias.float() if conv.bias is not None else w.new_zeros(cout)
+            b = cbias.float() if cbias is not None else w.new_zeros(cout)
         w = w.permute(0, 2, 3, 1)
         if pad_cin_to is not None and w.shape[3] < pad_cin_to:
             w = torch.nn.functional.pad(w, (0, pad_cin_to - w.shape[3]))
@@ -164,14 +166,26 @@ def cached_fold(conv, bn=None, pad_cin_to=None):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=False, groups=1, base_width=4):
+    def __init__(self, inplanes, planes, stride=1, downsample=False, groups=1, base_width=4, dcn=None):
         super().__init__()
         # ResNeXt (resnext.py:19-22): width = floor(planes * base_width / 64) * groups
         width = planes if groups == 1 else (planes * base_width // 64) * groups
         self.groups, self.width = groups, width
         self.conv1 = nn.Conv2d(inplanes, width, 1, stride=1, bias=False)
         self.bn1 = nn.BatchNorm2d(width)
-        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, groups=groups, bias=False)
+        # resnext.py:41-83: with `dcn` (and not `fallback_on_stride`) conv2 is a DeformConv fed by conv2_offset
+        self.with_dcn = dcn is not None and not dcn.get('fallback_on_stride', False)
+        if dcn is not None and dcn.get('modulated', False):
+            raise NotImplementedError('modulated')
+        if self.with_dcn:
+            self.dcn_groups = dcn.get('groups', 1)
+            self.conv2_offset = nn.Conv2d(width, dcn.get('deformable_groups', 1) * 18, 3, stride=stride,
+                                          padding=1)
+            self.conv2 = DeformConv(width, width, kernel_size=3, stride=stride, padding=1, dilation=1,
+                                    groups=self.dcn_groups,
+                                    deformable_groups=dcn.get('deformable_groups', 1), bias=False)
+        else:
+            self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, groups=groups, bias=False)
         self.bn2 = nn.BatchNorm2d(width)
         self.conv3 = nn.Conv2d(width, planes * 4, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4)
@@ -191,11 +205,21 @@ class Bottleneck(nn.Module):
                  c3=_fold_conv_bn(self.conv3, self.bn3))
         if self.downsample is not None:
             f['ds'] = _fold_conv_bn(self.downsample[0], self.downsample[1])
+        if self.with_dcn:
+            # the offset conv runs on the trunk's 3x3 conv path, which takes output channels in fours: 18 -> 20 with
+            # zero filter rows, once per fold; the deform kernels read the offsets at that pitch
+            ow, ob = _fold_conv_bn(self.conv2_offset, None)
+            padc = OFFSET_PITCH - ow.shape[0]
+            f['off'] = (torch.nn.functional.pad(ow, (0, 0, 0, 0, 0, 0, 0, padc)).contiguous(),
+                        torch.nn.functional.pad(ob, (0, padc)).contiguous())
         return f
 
     def run_bf16_storage(self, x, f):
         """The frozen block with bf16 activations in HBM (cfg[4] bf16 mode, csrc/conv_bf16s.hip):
         bf16 in, bf16 out, fp32 accumulate / bias / residual add / ReLU inside the kernels."""
+        if self.with_dcn:
+            raise NotImplementedError('Bottleneck.run_bf16_storage: a dcn block has no bf16-storage kernel '
+                                      '(the deformable conv is fp32 only)')
         identity, fk = x, None
         if 'ds' in f:
             if x.is_cuda and BF.shortcut_fork_enabled():      # projection shortcut beside conv1 / conv2 (see run)
@@ -247,13 +271,18 @@ class Bottleneck(nn.Module):
         #                                             the shortcut's epilogue gates the sum)
         # conv1 -> conv2 -> conv3 is a chain of single consumers: the ReLU backward of o1 / o2
         # rides in the epilogue of the next conv's dgrad (relu='consumers' + mask_input)
-        if self.groups > 1:      # ResNeXt: grouped 3x3 (csrc/grouped_conv.hip)
+        if self.groups > 1 or self.with_dcn:      # ResNeXt: grouped 3x3 (csrc/grouped_conv.hip) or its deformable form
             out = BF.conv2d_autograd(xin, f['c1'][0], f['c1'][1], relu=True, mask_input=first_mask,
                                      passthrough=first_pt)
             if first_pt:
                 out, identity = out
-            out = BF.grouped_conv3x3_nhwc(out, f['c2'][0], f['c2'][1], self.groups,
-                                          stride=self.stride, relu=True)
+            if self.with_dcn:    # resnet.py:237-239: offset = conv2_offset(out); out = conv2(out, offset) (+ bn2, ReLU)
+                off = BF.conv2d_autograd(out, f['off'][0], f['off'][1], stride=self.stride, pad=1)
+                out = BF.deform_conv3x3_nhwc(out, off, f['c2'][0], f['c2'][1], self.dcn_groups,
+                                             stride=self.stride, relu=True)
+            else:
+                out = BF.grouped_conv3x3_nhwc(out, f['c2'][0], f['c2'][1], self.groups,
+                                              stride=self.stride, relu=True)
             if fk is not None:
                 fk.join()
             return BF.conv2d_autograd(out, f['c3'][0], f['c3'][1], relu=out_relu, residual=identity)
@@ -359,6 +388,9 @@ class ResNet(nn.Module):
         for m in self.modules():
             if isinstance(m, Bottleneck):
                 nn.init.constant_(m.bn3.weight, 0)
+                if hasattr(m, 'conv2_offset'):       # resnet.py:506-510: constant_init(m.conv2_offset, 0)
+                    nn.init.constant_(m.conv2_offset.weight, 0)
+                    nn.init.constant_(m.conv2_offset.bias, 0)
 
     def _build_stem(self):
         return _fold_conv_bn(self.conv1, self.bn1, pad_cin_to=4)

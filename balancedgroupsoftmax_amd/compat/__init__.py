@@ -6,7 +6,10 @@ backed by ``libbgs.so``:
 * :mod:`.nms_cuda`       — ``mmdet/ops/nms/src/nms_cuda.cpp:8-17`` (``nms``; imported by
   ``mmdet/ops/nms/nms_wrapper.py:4``);
 * :mod:`.soft_nms_cpu`   — ``mmdet/ops/nms/src/soft_nms_cpu.pyx:22-127`` (``soft_nms_cpu``; imported by
-  ``mmdet/ops/nms/nms_wrapper.py:5``).  It runs on the current GPU despite its name.
+  ``mmdet/ops/nms/nms_wrapper.py:5``).  It runs on the current GPU despite its name;
+* :mod:`.deform_conv_cuda` — ``mmdet/ops/dcn/src/deform_conv_cuda.cpp:152-487`` (``deform_conv_forward_cuda`` /
+  ``deform_conv_backward_input_cuda`` / ``deform_conv_backward_parameters_cuda``; imported by
+  ``mmdet/ops/dcn/deform_conv.py:9``).  DCNv1 shapes of the BAGS configs only; the modulated entry points raise.
 
 A maintainer of the reference drops them in without touching any caller::
 
@@ -15,6 +18,7 @@ A maintainer of the reference drops them in without touching any caller::
     sys.modules['mmdet.ops.roi_align.roi_align_cuda'] = roi_align_cuda
     sys.modules['mmdet.ops.nms.nms_cuda'] = nms_cuda
     sys.modules['mmdet.ops.nms.soft_nms_cpu'] = soft_nms_cpu
+    sys.modules['mmdet.ops.dcn.deform_conv_cuda'] = compat.deform_conv_cuda
 
 Same argument order, layouts (NCHW features / outputs, unsorted ``dets``), ownership (the caller
 allocates ``output`` / ``bottom_grad``), return values (``1`` / ``0`` + "wrong roi size",
@@ -22,4 +26,4 @@ original-order keep indices) and input checks (CUDA + contiguous) as the extensi
 ABI underneath is NHWC / pre-sorted (``include/bgs.h``); the transposes and the score sort are done
 here, on the device.
 """
-from . import nms_cuda, roi_align_cuda, soft_nms_cpu  # noqa: F401
+from . import deform_conv_cuda, nms_cuda, roi_align_cuda, soft_nms_cpu  # noqa: F401

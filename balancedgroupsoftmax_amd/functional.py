@@ -1526,6 +1526,96 @@ def grouped_conv3x3_nhwc(x, w, bias, groups, stride=1, relu=False):
     return _grouped_conv3x3_launch(x, w, bias, groups, stride, relu)
 
 
+def _deform_conv3x3_launch(x, offset, w, bias, groups, stride, relu):
+    lib = capi.load()
+    N, H, W, C = x.shape
+    out = torch.empty((N, (H - 1) // stride + 1, (W - 1) // stride + 1, C), dtype=torch.float32,
+                      device=x.device)
+    rc = lib.bgs_deform_conv3x3_nhwc_f32(capi.ptr(x), capi.ptr(offset), capi.ptr(w), capi.ptr(bias),
+                                         capi.ptr(out), N, H, W, C, int(groups), 1, int(offset.shape[3]),
+                                         int(stride), int(bool(relu)), capi.current_stream(x.device))
+    capi.check('bgs_deform_conv3x3_nhwc_f32', rc)
+    return out
+
+
+class _DeformConvFn(torch.autograd.Function):
+    """Differentiable deformable 3x3 conv (+ bias + ReLU), csrc/deform_conv.hip: dx / doffset from one dgrad
+    launch (dx by float atomics into a zero-filled map, doffset in a fixed order), dw / db from the
+    chunk-reduced wgrad; the ReLU backward and the argument conventions are ``_GroupedConvFn``'s."""
+
+    @staticmethod
+    def forward(ctx, x, offset, w, bias, groups, stride, relu):
+        y = _deform_conv3x3_launch(x.detach(), offset.detach(), w.detach(),
+                                   None if bias is None else bias.detach(), groups, stride, relu)
+        ctx.cfg = (groups, stride, bool(relu), bias is not None)
+        ctx.save_for_backward(x, offset, w, y if relu else None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, offset, w, y = ctx.saved_tensors
+        groups, stride, relu, has_bias = ctx.cfg
+        lib = capi.load()
+        dz = dy.contiguous()
+        if relu:
+            dz = torch.ops.aten.threshold_backward(dz, y, 0.0)
+        N, H, W, C = x.shape
+        pitch = int(offset.shape[3])
+        st = capi.current_stream(x.device)
+        dx = doff = dw = db = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            dx = torch.zeros_like(x) if ctx.needs_input_grad[0] else None      # the kernel adds into it
+            doff = torch.zeros_like(offset) if ctx.needs_input_grad[1] else None  # (padding channels stay 0)
+            rc = lib.bgs_deform_conv3x3_dgrad_nhwc_f32(capi.ptr(x), capi.ptr(offset), capi.ptr(w), capi.ptr(dz),
+                                                       capi.ptr(dx), capi.ptr(doff), N, H, W, C, groups, 1,
+                                                       pitch, stride, st)
+            capi.check('bgs_deform_conv3x3_dgrad_nhwc_f32', rc)
+        want_b = has_bias and ctx.needs_input_grad[3]
+        if ctx.needs_input_grad[2] or want_b:
+            dw = torch.empty_like(w)
+            db = torch.empty((C,), dtype=torch.float32, device=x.device) if want_b else None
+            ws = _workspace(lib.bgs_deform_conv3x3_wgrad_workspace_bytes(N, H, W, C, groups, stride), x.device)
+            rc = lib.bgs_deform_conv3x3_wgrad_nhwc_f32(capi.ptr(x), capi.ptr(offset), capi.ptr(dz), capi.ptr(dw),
+                                                       capi.ptr(db), N, H, W, C, groups, 1, pitch, stride, 0,
+                                                       capi.ptr(ws), st)
+            capi.check('bgs_deform_conv3x3_wgrad_nhwc_f32', rc)
+        return dx, doff, dw, db, None, None, None
+
+
+def deform_conv3x3_nhwc(x, offset, w, bias, groups, stride=1, relu=False):
+    """Deformable 3x3 / pad 1 conv, DCNv1 with one deformable group (the reference's ``DeformConv``):
+    x ``[N,H,W,C]``, offset ``[N,Ho,Wo,pitch >= 18]`` (channel ``2 (3 i + j)`` = dh of tap ``(i, j)``, ``+ 1`` = dw),
+    w ``[C,3,3,C/groups]``; records an autograd node when an input requires grad."""
+    if x.dtype == torch.bfloat16 or offset.dtype == torch.bfloat16:
+        raise NotImplementedError('deform_conv3x3_nhwc: bf16-stored activations have no deformable kernel')
+    if _CONV_MATH[0] == 'bf16':
+        raise NotImplementedError("deform_conv3x3_nhwc: conv_math='bf16' has no deformable kernel")
+    _require_cuda(x, offset, w, bias)
+    for t in (x, offset, w) + (() if bias is None else (bias,)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('deform_conv3x3_nhwc: contiguous float32 tensors only')
+    if x.dim() != 4 or offset.dim() != 4:
+        raise ValueError('deform_conv3x3_nhwc: x [N,H,W,C] and offset [N,Ho,Wo,pitch]')
+    N, H, W, C = x.shape
+    stride = int(stride)
+    if stride not in (1, 2):
+        raise NotImplementedError('deform_conv3x3_nhwc: stride %d (1 and 2 have kernels)' % stride)
+    if C % groups or tuple(w.shape) != (C, 3, 3, C // groups):
+        raise ValueError('deform_conv3x3_nhwc: w must be [C,3,3,C/groups], got %s' % (tuple(w.shape),))
+    if C // groups not in (4, 8, 16, 32):
+        raise NotImplementedError('deform_conv3x3_nhwc: %d channels per group (4, 8, 16, 32 have kernels)'
+                                  % (C // groups))
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if tuple(offset.shape[:3]) != (N, Ho, Wo) or offset.shape[3] < 18:
+        raise ValueError('deform_conv3x3_nhwc: offset must be [%d,%d,%d,>=18], got %s'
+                         % (N, Ho, Wo, tuple(offset.shape)))
+    if torch.is_grad_enabled() and (x.requires_grad or offset.requires_grad or w.requires_grad or
+                                    (bias is not None and bias.requires_grad)):
+        return _DeformConvFn.apply(x, offset, w, bias, int(groups), stride, bool(relu))
+    return _deform_conv3x3_launch(x, offset, w, bias, groups, stride, relu)
+
+
 def nchw_to_nhwc4(img):
     """``[N, C <= 4, H, W]`` image batch -> ``[N, H, W, 4]`` fp32, channels zero-padded (the stem conv's
     16-byte pixels) in one launch (``bgs_nchw_to_nhwc4_f32``)."""

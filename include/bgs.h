@@ -440,6 +440,33 @@ int bgs_grouped_conv3x3_wgrad_nhwc_f32(const float* x, const float* dy, float* d
                                        int H, int W, int C, int groups, int stride, int accumulate,
                                        void* workspace, bgs_stream_t stream);
 
+/* Deformable 3x3 convolution, DCNv1 (csrc/deform_conv.hip): the reference's DeformConv
+ * (mmdet/ops/dcn/deform_conv.py, src/deform_conv_cuda_kernel.cu) as conv2 of the ResNeXt bottlenecks of
+ * gs_htc_dconv_c3-c5_*.  Pad 1, dilation 1, stride 1 or 2, deformable_groups = 1, C/groups in {4, 8, 16, 32};
+ * anything else is BGS_ERR_UNSUPPORTED.  x [N,H,W,C]; w [C,3,3,C/groups]; bias [C] or NULL;
+ * offset [N,Ho,Wo,off_pitch], off_pitch >= 18: channel 2 (3 i + j) = dh of tap (i, j), 2 (3 i + j) + 1 = dw
+ * (the reference's NCHW channel order on the last axis; channels >= 18 are padding); y [N,Ho,Wo,C].
+ * The sampled value is the reference's arithmetic operation for operation without FMA contraction
+ * (deform_conv_cuda_kernel.cu:84-114, 226-236); corner indices are computed only behind its range test, so a
+ * NaN / inf / huge offset is a zero tap and never an address.  One launch, no column buffer.
+ * dgrad: dz [N,Ho,Wo,C] (the gradient in front of the ReLU) -> dx [N,H,W,C] += (float atomics: the CALLER
+ *   zero-fills dx; last bits vary from run to run) and doffset [N,Ho,Wo,off_pitch] channels 0..17 = (fixed-order
+ *   sums: bitwise reproducible; padding channels are not written); either of dx / doffset may be NULL.
+ * wgrad: dw [C,3,3,C/groups] (+)= sum_m dz[m,co] sample(m, tap, ci); db [C] (+)= column sums of dz (db may be
+ *   NULL); fixed-order chunk reduction (bitwise reproducible);
+ *   workspace >= bgs_deform_conv3x3_wgrad_workspace_bytes(...). */
+int bgs_deform_conv3x3_nhwc_f32(const float* x, const float* offset, const float* w, const float* bias,
+                                float* y, int N, int H, int W, int C, int groups, int deformable_groups,
+                                int off_pitch, int stride, int relu, bgs_stream_t stream);
+int bgs_deform_conv3x3_dgrad_nhwc_f32(const float* x, const float* offset, const float* w, const float* dz,
+                                      float* dx, float* doffset, int N, int H, int W, int C, int groups,
+                                      int deformable_groups, int off_pitch, int stride, bgs_stream_t stream);
+size_t bgs_deform_conv3x3_wgrad_workspace_bytes(int N, int H, int W, int C, int groups, int stride);
+int bgs_deform_conv3x3_wgrad_nhwc_f32(const float* x, const float* offset, const float* dz, float* dw,
+                                      float* db, int N, int H, int W, int C, int groups, int deformable_groups,
+                                      int off_pitch, int stride, int accumulate, void* workspace,
+                                      bgs_stream_t stream);
+
 /* Image batch [N, C <= 4, H, W] fp32 (the reference's NCHW input, resnet.py:522) -> [N, H, W, 4] with the
  * channel axis zero-padded: the 16-byte-pixel input of the stem conv (one launch instead of pad + copy). */
 int bgs_nchw_to_nhwc4_f32(const float* x, float* y, int N, int C, int H, int W, bgs_stream_t stream);
