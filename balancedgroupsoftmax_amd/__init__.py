@@ -8,7 +8,10 @@ from . import (backbone, bbox_heads, checkpoint, config, detectors, gs_tables, l
 from .apis import inference_detector, init_detector
 from .builder import (build_backbone, build_detector, build_head, build_loss, build_neck,
                       build_roi_extractor, build_shared_head)
+from .bbox_heads import ReweightBBoxHead
 from .config import Config, ConfigDict
+from .functional import sigmoid_focal_loss, sigmoid_focal_loss_elementwise
+from .losses import FocalLoss
 from .lvis_eval import LVISEval, LVISGroundTruth, results2json
 from .ops import (DeformConv, DeformConvPack, ModulatedDeformConv, ModulatedDeformConvPack, deform_conv,
                   modulated_deform_conv)
@@ -24,4 +27,5 @@ __all__ = ['BACKBONES', 'DETECTORS', 'HEADS', 'LOSSES', 'NECKS', 'ROI_EXTRACTORS
            'Config', 'ConfigDict', 'LVISEval', 'LVISGroundTruth', 'lvis_eval', 'results2json',
            'TestPipeline', 'TrainPipeline', 'inference_detector', 'init_detector', 'rescale_size',
            'DeformConv', 'DeformConvPack', 'ModulatedDeformConv', 'ModulatedDeformConvPack', 'deform_conv',
-           'modulated_deform_conv']
+           'modulated_deform_conv', 'FocalLoss', 'ReweightBBoxHead', 'sigmoid_focal_loss',
+           'sigmoid_focal_loss_elementwise']

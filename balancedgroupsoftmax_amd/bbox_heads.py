@@ -393,6 +393,58 @@ class SharedFCBBoxHead(ConvFCBBoxHead):
 
 
 @HEADS.register_module
+class ReweightBBoxHead(SharedFCBBoxHead):
+    """``SharedFCBBoxHead`` with per-class loss weights (reweight_bbox_head.py:15-70; the transferred baselines).
+
+    ``reweight_cfg.cls_weight`` names a ``torch.load``-able ``[num_classes]`` tensor.  It is a plain attribute in the
+    reference (not in its state dict), here a non-persistent buffer: the state-dict names are ``SharedFCBBoxHead``'s.
+    ``loss()`` weighs row ``r`` by ``cls_weight[labels[r]]`` and normalises by ``max(#(label_weights > 0), 1)``
+    (:48-56); the box branch is the shared one.  ``(label_weights > 0)`` is multiplied in, so the padding slots of a
+    fixed-shape batch are left out (the reference's sampler never produces any).  No host sync, no boolean indexing:
+    with ``CrossEntropyLoss`` the weights ride as row weights of the one-bin GroupSoftmax launch, with ``FocalLoss``
+    the table goes to the focal kernel, which gathers it by label behind a range test."""
+
+    def __init__(self, num_fcs=2, fc_out_channels=1024, reweight_cfg=None, *args, **kwargs):
+        super().__init__(num_fcs=num_fcs, fc_out_channels=fc_out_channels, *args, **kwargs)
+        if reweight_cfg is None:
+            raise ValueError('ReweightBBoxHead needs reweight_cfg=dict(cls_weight=<path>)')
+        path = reweight_cfg['cls_weight'] if isinstance(reweight_cfg, dict) else reweight_cfg.cls_weight
+        w = torch.as_tensor(torch.load(path, map_location='cpu')).to(torch.float32).reshape(-1)
+        if w.numel() != self.num_classes:
+            raise ValueError('reweight_cfg.cls_weight holds %d weights, the head has %d classes'
+                             % (w.numel(), self.num_classes))
+        self.register_buffer('cls_weight', w.contiguous(), persistent=False)
+
+    def _reweight(self, labels):
+        return self.cls_weight[labels.clamp(0, self.num_classes - 1)]
+
+    @force_fp32(apply_to=('cls_score', 'bbox_pred'))
+    def loss(self, cls_score, bbox_pred, labels, label_weights, bbox_targets, bbox_weights,
+             reduction_override=None):
+        losses = dict()
+        if cls_score is not None:
+            real = (label_weights > 0).to(torch.float32)
+            avg_factor = torch.clamp(real.sum(), min=1.)
+            kind = type(self.loss_cls).__name__
+            if kind == 'FocalLoss':
+                losses['loss_cls'] = self.loss_cls(cls_score, labels, real, avg_factor=avg_factor,
+                                                   reduction_override=reduction_override,
+                                                   cls_weight=self.cls_weight)
+            elif kind == 'CrossEntropyLoss':
+                losses['loss_cls'] = self.loss_cls(cls_score, labels, self._reweight(labels) * real,
+                                                   avg_factor=avg_factor,
+                                                   reduction_override=reduction_override)
+            else:
+                raise NotImplementedError('ReweightBBoxHead: loss_cls %s (CrossEntropyLoss and FocalLoss have '
+                                          'kernels)' % kind)
+            losses['acc'] = accuracy(cls_score, labels)
+        if bbox_pred is not None:
+            losses['loss_bbox'] = self._loss_bbox(bbox_pred, labels, bbox_targets, bbox_weights,
+                                                  reduction_override, label_weights)
+        return losses
+
+
+@HEADS.register_module
 class GSBBoxHeadWith0(SharedFCBBoxHead):
     """Balanced Group Softmax box head (gs_bbox_head_with0.py:15-380).
 

@@ -146,6 +146,14 @@ SIGNATURES = {
     'bgs_deform_conv3x3_dgrad_nhwc_f32': (ctypes.c_int, [c_f32p] * 6 + [ctypes.c_int] * 8 + [c_ptr]),
     'bgs_deform_conv3x3_wgrad_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 6),
     'bgs_deform_conv3x3_wgrad_nhwc_f32': (ctypes.c_int, [c_f32p] * 5 + [ctypes.c_int] * 9 + [c_ptr, c_ptr]),
+    'bgs_sigmoid_focal_workspace_bytes': (ctypes.c_size_t, []),
+    'bgs_sigmoid_focal_fwd': (ctypes.c_int, [c_f32p, ctypes.c_longlong, c_i64p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_float, ctypes.c_float, ctypes.c_int, c_f32p, c_ptr]),
+    'bgs_sigmoid_focal_bwd': (ctypes.c_int, [c_f32p, ctypes.c_longlong, c_i64p, c_f32p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_float, ctypes.c_float, ctypes.c_int, c_f32p, c_ptr]),
+    'bgs_sigmoid_focal_fwd_bwd': (ctypes.c_int, [c_f32p, ctypes.c_longlong, c_i64p, c_f32p, c_f32p, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int, c_f32p,
+                                                 ctypes.c_float, c_f32p, c_f32p, c_ptr, c_ptr]),
     'bgs_maxpool3x3s2_bwd_nhwc_f32': (ctypes.c_int, [c_f32p, c_f32p, c_f32p] + [ctypes.c_int] * 4 + [c_ptr]),
     'bgs_maxpool3x3s2_nhwc_f32': (ctypes.c_int, [c_f32p, c_f32p] + [ctypes.c_int] * 4 + [c_ptr]),
     'bgs_nchw_to_nhwc4_f32': (ctypes.c_int, [c_f32p, c_f32p] + [ctypes.c_int] * 4 + [c_ptr]),

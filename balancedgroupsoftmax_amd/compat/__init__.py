@@ -9,7 +9,9 @@ backed by ``libbgs.so``:
   ``mmdet/ops/nms/nms_wrapper.py:5``).  It runs on the current GPU despite its name;
 * :mod:`.deform_conv_cuda` — ``mmdet/ops/dcn/src/deform_conv_cuda.cpp:152-487`` (``deform_conv_forward_cuda`` /
   ``deform_conv_backward_input_cuda`` / ``deform_conv_backward_parameters_cuda``; imported by
-  ``mmdet/ops/dcn/deform_conv.py:9``).  DCNv1 shapes of the BAGS configs only; the modulated entry points raise.
+  ``mmdet/ops/dcn/deform_conv.py:9``).  DCNv1 shapes of the BAGS configs only; the modulated entry points raise;
+* :mod:`.sigmoid_focal_loss_cuda` — ``mmdet/ops/sigmoid_focal_loss/src/sigmoid_focal_loss.cpp:18-45`` (``forward`` /
+  ``backward``; imported by ``mmdet/ops/sigmoid_focal_loss/sigmoid_focal_loss.py:5``).  Float32, one label per row.
 
 A maintainer of the reference drops them in without touching any caller::
 
@@ -19,6 +21,7 @@ A maintainer of the reference drops them in without touching any caller::
     sys.modules['mmdet.ops.nms.nms_cuda'] = nms_cuda
     sys.modules['mmdet.ops.nms.soft_nms_cpu'] = soft_nms_cpu
     sys.modules['mmdet.ops.dcn.deform_conv_cuda'] = compat.deform_conv_cuda
+    sys.modules['mmdet.ops.sigmoid_focal_loss.sigmoid_focal_loss_cuda'] = compat.sigmoid_focal_loss_cuda
 
 Same argument order, layouts (NCHW features / outputs, unsorted ``dets``), ownership (the caller
 allocates ``output`` / ``bottom_grad``), return values (``1`` / ``0`` + "wrong roi size",
@@ -26,4 +29,4 @@ original-order keep indices) and input checks (CUDA + contiguous) as the extensi
 ABI underneath is NHWC / pre-sorted (``include/bgs.h``); the transposes and the score sort are done
 here, on the device.
 """
-from . import deform_conv_cuda, nms_cuda, roi_align_cuda, soft_nms_cpu  # noqa: F401
+from . import deform_conv_cuda, nms_cuda, roi_align_cuda, sigmoid_focal_loss_cuda, soft_nms_cpu  # noqa: F401

@@ -35,6 +35,8 @@ EXTRA_VARIANTS = {
     'p3ntay': dict(name='libbgs_p3ntay.so', flags=['-DBGS_P3_A_AUX=2', '-DBGS_P3_Y_AUX=2']),
     # timing-only ablations of the 3x3 planes kernel: 1 = filter fragments from L2 twice per chunk instead of 18 times,
     # 2 = the patch loaded once, 3 = both (results are wrong; tools/planes3_ablate.sh)
+    # the focal loss element arithmetic in float instead of double (A/B arm of tools/focal_loss_time.py)
+    'focalf32': dict(name='libbgs_focalf32.so', flags=['-DBGS_FOCAL_F32']),
     'p3prio': dict(name='libbgs_p3prio.so', flags=['-DBGS_P3_PRIO=1']),
     'p3abl1': dict(name='libbgs_p3abl1.so', flags=['-DBGS_P3_ABL=1']),
     'p3abl2': dict(name='libbgs_p3abl2.so', flags=['-DBGS_P3_ABL=2']),

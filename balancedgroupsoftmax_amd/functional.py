@@ -595,6 +595,124 @@ def bbox_smooth_l1_loss(bbox_pred, labels, bbox_targets, bbox_weights, num_reg_c
                                loss_weight)
 
 
+# ----------------------------------------------------------------------------------------
+# sigmoid focal loss  (mmdet/ops/sigmoid_focal_loss, mmdet/models/losses/focal_loss.py)
+# ----------------------------------------------------------------------------------------
+def _focal_inputs(name, logits, labels, gamma, pos_shift):
+    """Checked (float32 logits with unit column stride, row stride, contiguous int64 labels)."""
+    if logits.dim() != 2:
+        raise ValueError('%s: logits must be [N, C], got %s' % (name, tuple(logits.shape)))
+    if logits.dtype != torch.float32:
+        raise NotImplementedError('%s: %s logits have no kernel (float32 does)' % (name, logits.dtype))
+    if labels.dtype != torch.int64 or labels.dim() != 1 or labels.numel() != logits.shape[0]:
+        raise ValueError('%s: labels must be int64 [N]' % name)
+    if pos_shift not in (0, 1):
+        raise ValueError('%s: pos_shift must be 0 or 1' % name)
+    if not float(gamma) >= 0.0:
+        raise ValueError('%s: gamma must be >= 0' % name)
+    if logits.shape[0] * logits.shape[1] >= 2 ** 31:
+        raise NotImplementedError('%s: N * C >= 2^31' % name)
+    z = logits.detach()
+    if z.shape[0] > 1 and (z.stride(1) != 1 or z.stride(0) < z.shape[1]) or z.shape[0] <= 1 and not z.is_contiguous():
+        z = z.contiguous()
+    ld = z.stride(0) if z.shape[0] > 1 else z.shape[1]
+    return z, int(ld), labels.contiguous()
+
+
+class _SigmoidFocalLoss(torch.autograd.Function):
+    """Reduced loss and dense gradient from ONE launch (``bgs_sigmoid_focal_fwd_bwd``); backward only scales the
+    kept ``dlogits`` by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, row_weights, cls_weight, gamma, alpha, avg, loss_weight, pos_shift):
+        lib = capi.load()
+        z, ld, labels = _focal_inputs('sigmoid_focal_loss', logits, labels, gamma, pos_shift)
+        N, C = z.shape
+        dev = z.device
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        dlogits = torch.empty((N, C), dtype=torch.float32, device=dev) if logits.requires_grad else None
+        ws = _workspace(lib.bgs_sigmoid_focal_workspace_bytes(), dev)
+        rc = lib.bgs_sigmoid_focal_fwd_bwd(capi.ptr(z), ld, capi.ptr(labels), capi.ptr(row_weights),
+                                           capi.ptr(cls_weight), N, C, float(gamma), float(alpha), int(pos_shift),
+                                           capi.ptr(avg), float(loss_weight), capi.ptr(loss), capi.ptr(dlogits),
+                                           capi.ptr(ws), capi.current_stream(dev))
+        capi.check('bgs_sigmoid_focal_fwd_bwd', rc)
+        ctx.dlogits = dlogits
+        return loss[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        if ctx.dlogits is None:
+            return (None,) * 9
+        return (ctx.dlogits * grad_loss,) + (None,) * 8
+
+
+def sigmoid_focal_loss(logits, labels, row_weights=None, cls_weight=None, gamma=2.0, alpha=0.25, avg=None,
+                       loss_weight=1.0, pos_shift=0):
+    """``loss_weight * sum_r w_r sum_d focal(logits[r, d]) / avg`` as a scalar, differentiable w.r.t. ``logits``.
+
+    ``labels [N] i64``: the positive column of row ``r`` is ``labels[r] - pos_shift`` when that lies in ``[0, C)``,
+    otherwise the row has none.  ``w_r = row_weights[r] * cls_weight[labels[r]]`` (either may be ``None`` = 1); the
+    gather runs inside the kernel and a label outside ``[0, C)`` gets weight 0.  ``avg``: a number, a device float
+    tensor ``[1]`` (no sync), or ``None`` = ``N * C``."""
+    _require_cuda(logits, labels, row_weights, cls_weight)
+    N, C = logits.shape
+    if row_weights is not None:
+        row_weights = _f32c(row_weights).reshape(-1)
+        if row_weights.numel() != N:
+            raise ValueError('sigmoid_focal_loss: row_weights must hold N values')
+    if cls_weight is not None:
+        cls_weight = _f32c(cls_weight).reshape(-1)
+        if cls_weight.numel() != C:
+            raise ValueError('sigmoid_focal_loss: cls_weight must hold C values')
+    if avg is not None:
+        if isinstance(avg, torch.Tensor):
+            _require_cuda(avg)
+            avg = _f32c(avg).reshape(-1)[:1]
+        else:
+            avg = torch.full((1,), float(avg), dtype=torch.float32, device=logits.device)
+    return _SigmoidFocalLoss.apply(logits, labels, row_weights, cls_weight, gamma, alpha, avg, loss_weight,
+                                   pos_shift)
+
+
+class _SigmoidFocalElementwise(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, logits, labels, gamma, alpha, pos_shift):
+        lib = capi.load()
+        z, ld, labels = _focal_inputs('sigmoid_focal_loss_elementwise', logits, labels, gamma, pos_shift)
+        N, C = z.shape
+        losses = torch.empty((N, C), dtype=torch.float32, device=z.device)
+        rc = lib.bgs_sigmoid_focal_fwd(capi.ptr(z), ld, capi.ptr(labels), N, C, float(gamma), float(alpha),
+                                       int(pos_shift), capi.ptr(losses), capi.current_stream(z.device))
+        capi.check('bgs_sigmoid_focal_fwd', rc)
+        ctx.save_for_backward(z, labels)
+        ctx.cfg = (ld, float(gamma), float(alpha), int(pos_shift))
+        return losses
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_losses):
+        z, labels = ctx.saved_tensors
+        ld, gamma, alpha, pos_shift = ctx.cfg
+        lib = capi.load()
+        N, C = z.shape
+        d = _f32c(d_losses)
+        d_logits = torch.empty((N, C), dtype=torch.float32, device=z.device)
+        rc = lib.bgs_sigmoid_focal_bwd(capi.ptr(z), ld, capi.ptr(labels), capi.ptr(d), N, C, gamma, alpha,
+                                       pos_shift, capi.ptr(d_logits), capi.current_stream(z.device))
+        capi.check('bgs_sigmoid_focal_bwd', rc)
+        return d_logits, None, None, None, None
+
+
+def sigmoid_focal_loss_elementwise(logits, labels, gamma=2.0, alpha=0.25, pos_shift=0):
+    """The unreduced ``[N, C]`` focal losses (``bgs_sigmoid_focal_fwd``), differentiable through
+    ``bgs_sigmoid_focal_bwd``; label convention of :func:`sigmoid_focal_loss`."""
+    _require_cuda(logits, labels)
+    return _SigmoidFocalElementwise.apply(logits, labels, gamma, alpha, pos_shift)
+
+
 def fc_reg_gather_enabled():
     """A frozen class-specific ``fc_reg`` computes only the four columns of each RoI's own class
     (``ConvFCBBoxHead.forward(reg_labels=...)``): ``BGS_FC_REG_GATHER=0`` (read per call) keeps the dense launch."""

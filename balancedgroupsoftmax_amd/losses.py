@@ -137,6 +137,68 @@ class SmoothL1Loss(nn.Module):
         return val if div is None else val / div
 
 
+@LOSSES.register_module
+class FocalLoss(nn.Module):
+    """Registry key, ctor kwargs and call signature of the reference (focal_loss.py:46-90), on the fused HIP kernel
+    ``bgs_sigmoid_focal_fwd_bwd`` (``reduction='none'``: the elementwise kernels).
+
+    **A defect of the reference that is NOT reproduced.**  Its ``forward`` builds ``F.one_hot(target, 1231)``, forces
+    ``avg_factor = N * 1231`` and hands the ``[N, 1231]`` one-hot matrix to the CUDA op, which expects ``[N]`` class
+    labels: the op reads ``targets[n]`` for ``n < N``, i.e. the first ``N`` entries of the flattened one-hot, so every
+    row trains as all-negative except where such an entry happens to be 1 (recorded by executing the reference:
+    ``shipped_path/*`` of ``tests/golden/focal_loss_golden.npz``).  The contract here is what the module builds and
+    evidently means — the reference's own ``py_sigmoid_focal_loss(pred, one_hot(label, C), weight.view(-1, 1), gamma,
+    alpha, reduction, avg_factor)``:
+
+    * the positive column of a row is its label, column 0 for background included;
+    * ``avg_factor`` is overridden to ``N * C`` whatever the caller passed, with ``C = pred.shape[1]`` rather than
+      the literal 1231;
+    * in a fixed-shape batch, rows with ``weight <= 0`` are padding: they carry weight 0 and ``N`` counts the real
+      rows only (computed on the device, no sync; the reference's sampler never produces such rows);
+    * ``reduction='sum'`` is the reference's ``ValueError`` (an ``avg_factor`` is always present), ``use_sigmoid=False``
+      its assertion.
+
+    Saturation: the stable log forms do not clamp at ``log(FLT_MIN)`` as the reference's kernel does; parity holds
+    for ``|logit| <= 80`` (``include/bgs.h``)."""
+
+    def __init__(self, use_sigmoid=True, gamma=2.0, alpha=0.25, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        assert use_sigmoid is True, 'Only sigmoid focal loss supported now.'
+        self.use_sigmoid = use_sigmoid
+        self.gamma, self.alpha = gamma, alpha
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, cls_weight=None):
+        """``cls_weight [C]`` (not in the reference's signature; ``ReweightBBoxHead`` passes it): per-class weights
+        gathered by the row's label inside the kernel and multiplied into ``weight``."""
+        from . import functional as BF
+        assert reduction_override in _REDUCTIONS
+        red = reduction_override or self.reduction
+        if red == 'sum':
+            raise ValueError('avg_factor can not be used with reduction="sum"')
+        BF._require_cuda(pred, target, weight, cls_weight)
+        if red == 'none':
+            out = BF.sigmoid_focal_loss_elementwise(pred, target, self.gamma, self.alpha)
+            w = None if weight is None else weight.to(torch.float32).reshape(-1)
+            if cls_weight is not None:
+                ok = (target >= 0) & (target < pred.shape[1])
+                cw = cls_weight.to(torch.float32)[target.clamp(0, pred.shape[1] - 1)] * ok
+                w = cw if w is None else w * cw
+            if w is not None:
+                out = out * w.clamp(min=0).view(-1, 1)
+            return self.loss_weight * out
+        if red != 'mean':
+            raise ValueError('unknown reduction %r' % (red,))
+        n, c = pred.shape
+        if weight is None:
+            rw, avg = None, float(max(n * c, 1))
+        else:
+            rw = weight.to(torch.float32).reshape(-1).clamp(min=0)
+            avg = ((weight.reshape(-1) > 0).sum().to(torch.float32) * float(c)).clamp(min=1.0).reshape(1)
+        return BF.sigmoid_focal_loss(pred, target, rw, cls_weight, gamma=self.gamma, alpha=self.alpha, avg=avg,
+                                     loss_weight=self.loss_weight, pos_shift=0)
+
+
 def accuracy(pred, target, topk=1):
     """Top-k accuracy in percent (mmdet/models/losses/accuracy.py); ``acc`` key of BBoxHead.loss."""
     ks = (topk,) if isinstance(topk, int) else tuple(topk)

@@ -467,6 +467,41 @@ int bgs_deform_conv3x3_wgrad_nhwc_f32(const float* x, const float* offset, const
                                       int off_pitch, int stride, int accumulate, void* workspace,
                                       bgs_stream_t stream);
 
+/* Sigmoid focal loss (csrc/focal_loss.hip): the reference's extension mmdet/ops/sigmoid_focal_loss
+ * (src/sigmoid_focal_loss_cuda.cu:24-97) and the loss module on top of it (mmdet/models/losses/focal_loss.py).
+ * With p = sigmoid(x), g = gamma, for row r and column d:
+ *   d is the positive column:  loss = -alpha (1-p)^g log p         grad = -alpha (1-p)^g (1 - p - g p log p)
+ *   every other column:        loss = -(1-alpha) p^g log(1-p)      grad = -(1-alpha) p^g (g (1-p) log(1-p) - p)
+ * both logs in their stable softplus forms (log p = -softplus(-x), log(1-p) = -softplus(x)).
+ *   logits [N,C] float, row stride ld >= C (elements); labels [N] int64; pos_shift in {0, 1}.
+ *   Positive column of row r: labels[r] - pos_shift when that lies in [0, C), otherwise the row has none.  Labels
+ *   are only compared with a column index (pos_shift = 1 is the extension's own convention: target 0 = no positive;
+ *   pos_shift = 0 the one-hot of the label, column 0 for background included).
+ *   gamma >= 0: 2 and 0.5 (the shipped values) take exact p * p and sqrt arms, 0 the factor 1, anything else
+ *   exp(gamma log p); the arm is chosen on the host.
+ * bgs_sigmoid_focal_fwd: losses [N,C].  bgs_sigmoid_focal_bwd: d_logits [N,C] = grad * d_losses [N,C].
+ * bgs_sigmoid_focal_fwd_bwd: loss and dense gradient in ONE pass over the logits:
+ *   w_r = row_weights[r] (NULL: 1) * cls_weight[labels[r]] (NULL: 1; a label outside [0, C) gives weight 0 — the
+ *         gather happens inside the kernel, behind the range test);
+ *   loss_out[0]  = loss_weight * sum_r w_r sum_d loss[r,d] / avg[0]      (avg: device float [1], NULL = N * C)
+ *   dlogits[r,d] = grad[r,d] * ((w_r * loss_weight) / avg[0])            ([N,C] contiguous, or NULL: forward only)
+ *     — bitwise what bgs_sigmoid_focal_bwd gives for d_losses[r,d] = (w_r * loss_weight) / avg;
+ *   workspace: bgs_sigmoid_focal_workspace_bytes() bytes (per-workgroup partial sums, reduced in a fixed order by
+ *   a second tiny launch: two calls return the same bits; no atomics).  N == 0: loss 0, no kernel.
+ * N * C >= 2^31 is BGS_ERR_UNSUPPORTED.
+ * Deviation from the reference: it clamps log(max(p, FLT_MIN)) with p rounded to float, so that below x = -87.3
+ * its positive term saturates at 87.34 alpha; the stable form does not and returns alpha |x| there.  Contract
+ * domain for parity with the reference: |x| <= 80.  Non-finite logits are out of contract. */
+size_t bgs_sigmoid_focal_workspace_bytes(void);
+int bgs_sigmoid_focal_fwd(const float* logits, long long ld, const int64_t* labels, int N, int C, float gamma,
+                          float alpha, int pos_shift, float* losses, bgs_stream_t stream);
+int bgs_sigmoid_focal_bwd(const float* logits, long long ld, const int64_t* labels, const float* d_losses, int N,
+                          int C, float gamma, float alpha, int pos_shift, float* d_logits, bgs_stream_t stream);
+int bgs_sigmoid_focal_fwd_bwd(const float* logits, long long ld, const int64_t* labels, const float* row_weights,
+                              const float* cls_weight, int N, int C, float gamma, float alpha, int pos_shift,
+                              const float* avg, float loss_weight, float* loss_out, float* dlogits, void* workspace,
+                              bgs_stream_t stream);
+
 /* Image batch [N, C <= 4, H, W] fp32 (the reference's NCHW input, resnet.py:522) -> [N, H, W, 4] with the
  * channel axis zero-padded: the 16-byte-pixel input of the stem conv (one launch instead of pad + copy). */
 int bgs_nchw_to_nhwc4_f32(const float* x, float* y, int N, int C, int H, int W, bgs_stream_t stream);
