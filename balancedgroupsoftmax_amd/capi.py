@@ -214,6 +214,16 @@ SIGNATURES = {
     'bgs_lvis_match_workspace_bytes': (ctypes.c_size_t, [ctypes.c_longlong, ctypes.c_int, ctypes.c_int]),
     'bgs_lvis_match': (ctypes.c_int, [c_ptr] * 4 + [ctypes.c_int] + [ctypes.c_longlong] * 2 + [c_ptr] * 4
                        + [c_ptr, ctypes.c_int, c_ptr, ctypes.c_int, c_ptr, ctypes.c_size_t] + [c_ptr] * 4 + [c_ptr]),
+    'bgs_poly_rle_edge_points': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.c_longlong, ctypes.c_int, c_ptr, c_ptr]),
+    'bgs_poly_rle_crossings': (ctypes.c_int, [c_ptr] * 4 + [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_ptr, c_ptr,
+                                              ctypes.c_longlong, c_ptr, c_ptr, c_ptr]),
+    'bgs_poly_rle_events_from_transitions': (ctypes.c_int, [c_ptr] * 4 + [ctypes.c_int, ctypes.c_longlong, c_ptr,
+                                                            c_ptr]),
+    'bgs_poly_rle_events_from_runs': (ctypes.c_int, [c_ptr] * 3 + [ctypes.c_int, ctypes.c_longlong, c_ptr, c_ptr]),
+    'bgs_poly_rle_resolve': (ctypes.c_int, [c_ptr] * 3 + [ctypes.c_int, ctypes.c_int] + [c_ptr] * 4
+                             + [ctypes.c_int, ctypes.c_longlong] + [c_ptr] * 4),
+    'bgs_poly_rle_write': (ctypes.c_int, [c_ptr] * 4 + [ctypes.c_int] + [c_ptr] * 4
+                           + [ctypes.c_longlong, c_ptr, ctypes.c_longlong, c_ptr, c_ptr]),
     'bgs_mask_gt_logits': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_ptr, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, c_f32p, c_ptr]),
     'bgs_mask_bce_partials': (ctypes.c_int, [ctypes.c_int]),

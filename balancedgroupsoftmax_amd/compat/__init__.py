@@ -11,7 +11,10 @@ backed by ``libbgs.so``:
   ``deform_conv_backward_input_cuda`` / ``deform_conv_backward_parameters_cuda``; imported by
   ``mmdet/ops/dcn/deform_conv.py:9``).  DCNv1 shapes of the BAGS configs only; the modulated entry points raise;
 * :mod:`.sigmoid_focal_loss_cuda` — ``mmdet/ops/sigmoid_focal_loss/src/sigmoid_focal_loss.cpp:18-45`` (``forward`` /
-  ``backward``; imported by ``mmdet/ops/sigmoid_focal_loss/sigmoid_focal_loss.py:5``).  Float32, one label per row.
+  ``backward``; imported by ``mmdet/ops/sigmoid_focal_loss/sigmoid_focal_loss.py:5``).  Float32, one label per row;
+* :mod:`.pycocotools_mask` — ``pycocotools.mask`` as far as the ground-truth path reaches it (``frPyObjects`` for
+  polygons and uncompressed RLEs, ``merge``, ``decode``, ``area``; imported by
+  ``mmdet/datasets/pipelines/loading.py:6`` and ``lvis-api/lvis/lvis.py``).  A restatement of maskApi.c, see the module.
 
 A maintainer of the reference drops them in without touching any caller::
 
@@ -29,4 +32,5 @@ original-order keep indices) and input checks (CUDA + contiguous) as the extensi
 ABI underneath is NHWC / pre-sorted (``include/bgs.h``); the transposes and the score sort are done
 here, on the device.
 """
-from . import deform_conv_cuda, nms_cuda, roi_align_cuda, sigmoid_focal_loss_cuda, soft_nms_cpu  # noqa: F401
+from . import (deform_conv_cuda, nms_cuda, pycocotools_mask, roi_align_cuda, sigmoid_focal_loss_cuda,  # noqa: F401
+               soft_nms_cpu)

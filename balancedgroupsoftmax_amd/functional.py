@@ -2757,6 +2757,253 @@ def mask_rle(probs, boxes, scale_factor, thr, img_hw):
 
 
 # ----------------------------------------------------------------------------------------
+# polygons -> COCO RLE, RLE merge  (pycocotools maskApi.c rleFrPoly / rleMerge; csrc/poly_rle.hip)
+# ----------------------------------------------------------------------------------------
+POLY_COORD_LIMIT = 1e6
+RLE_MAX_AREA = 2 ** 31 - 1
+_RLE_PARITY, _RLE_UNION, _RLE_INTERSECT = 0, 1, 2
+
+
+def _poly_tables(objects, sizes):
+    """The host checks and the flat tables of :func:`poly_rle_counts`: ``(xy float64 [2 V], part_off int64 [P + 1],
+    obj_off int64 [O + 1], hw int32 [O, 2])``."""
+    import numpy as np
+    objects = list(objects)
+    O = len(objects)
+    hw = np.asarray(sizes, dtype=np.int64).reshape(-1, 2) if O else np.zeros((0, 2), np.int64)
+    if hw.shape[0] == 1 and O > 1:
+        hw = np.broadcast_to(hw, (O, 2))
+    if hw.shape[0] != O:
+        raise ValueError('poly_rle: %d objects but %d sizes' % (O, hw.shape[0]))
+    if O and hw.min() <= 0:
+        raise ValueError('poly_rle: image sizes must be positive')
+    if O and (hw[:, 0] * hw[:, 1]).max() > RLE_MAX_AREA:
+        raise ValueError('poly_rle: h * w must not exceed 2^31 - 1 (column-major positions are 32 bit)')
+    parts = []
+    nparts = np.zeros(O, np.int64)
+    for o, obj in enumerate(objects):
+        if not isinstance(obj, (list, tuple)) or (len(obj) and not hasattr(obj[0], '__len__')):
+            raise ValueError('poly_rle: object %d is not a list of parts (flat coordinate lists)' % o)
+        nparts[o] = len(obj)
+        parts.extend(obj)
+    lens = np.fromiter((len(p) for p in parts), dtype=np.int64, count=len(parts))
+    if lens.size and (lens.min() == 0 or (lens & 1).any()):
+        raise ValueError('poly_rle: a part needs a non-empty, even number of coordinates (x0, y0, x1, y1, ...)')
+    xy = np.fromiter(itertools.chain.from_iterable(parts), dtype=np.float64, count=int(lens.sum()))
+    if xy.size and not (np.isfinite(xy).all() and np.abs(xy).max() <= POLY_COORD_LIMIT):
+        raise ValueError('poly_rle: coordinates must be finite and within +-%g' % POLY_COORD_LIMIT)
+    part_off = np.zeros(lens.size + 1, np.int64)
+    np.cumsum(lens // 2, out=part_off[1:])
+    obj_off = np.zeros(O + 1, np.int64)
+    np.cumsum(nparts, out=obj_off[1:])
+    return xy, part_off, obj_off, np.ascontiguousarray(hw, dtype=np.int32)
+
+
+def _rle_device(device, what):
+    if not torch.cuda.is_available():
+        raise RuntimeError('%s runs only on the GPU (hand-written HIP kernels); there is no CPU fallback' % what)
+    dev = torch.device('cuda' if device is None else device)
+    if dev.type != 'cuda':
+        raise RuntimeError('%s runs only on the GPU (hand-written HIP kernels); got device %s' % (what, dev))
+    return torch.device('cuda', torch.cuda.current_device()) if dev.index is None else dev
+
+
+def _scan0(x):
+    """int tensor ``[n]`` -> its exclusive scan, int64 ``[n + 1]``."""
+    out = torch.zeros(x.shape[0] + 1, dtype=torch.int64, device=x.device)
+    out[1:] = torch.cumsum(x, 0, dtype=torch.int64)
+    return out
+
+
+def _np_ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _rle_finish(lib, S, bound, dev, runs, write):
+    """``runs`` int32 ``[S]`` on the device -> the host pair ``(counts uint32 [total], offsets int64 [S + 1])``:
+    the offsets and the counts share one device buffer (``bound`` >= total) and come back in ONE copy."""
+    import numpy as np
+    head = 2 * (S + 1)
+    out = torch.empty(head + bound, dtype=torch.int32, device=dev)
+    out_off = out[:head].view(torch.int64)
+    out_off[:1].zero_()
+    out_off[1:] = torch.cumsum(runs, 0, dtype=torch.int64)
+    write(out_off, out[head:])
+    host = out.cpu().numpy()
+    offsets = host[:head].view(np.int64).copy()
+    total = int(offsets[-1])
+    return host[head:head + total].view(np.uint32).copy(), offsets
+
+
+def poly_rle_counts(objects, sizes, device=None):
+    """Polygons -> COCO run lengths on the device (``rleFrPoly`` of every part, then ``rleMerge`` of an object's
+    parts: what ``pycocotools.mask.frPyObjects`` + ``merge`` give; csrc/poly_rle.hip).  ``objects``: a list of ``O``
+    objects, each a list of parts, each a flat ``[x0, y0, x1, y1, ...]``; ``sizes``: ``(h, w)`` or ``[O, 2]``.
+    Returns the host triple of :func:`mask_rle_counts`: ``(counts uint32 [total], offsets int64 [O + 1], sizes int32
+    [O, 2])``.  Seven launches whatever ``O`` is, one host read (the number of boundary crossings, which sizes the
+    buffers) and one copy back; bitwise the same on every call."""
+    return poly_rle_counts_from_tables(*_poly_tables(objects, sizes), device=device)
+
+
+def poly_rle_counts_from_tables(xy, part_off, obj_off, hw, device=None):
+    """:func:`poly_rle_counts` on the flat host tables (``_poly_tables``: ``xy`` float64 ``[2 V]``, ``part_off`` int64
+    ``[P + 1]`` in vertices, ``obj_off`` int64 ``[O + 1]`` in parts, ``hw`` int32 ``[O, 2]``, already checked)."""
+    import numpy as np
+    O, P, V = hw.shape[0], part_off.size - 1, xy.size // 2
+    if O == 0:
+        return np.zeros(0, np.uint32), np.zeros(1, np.int64), hw
+    dev = _rle_device(device, 'poly_rle')
+    if P == 0:                                             # only empty masks
+        return ((hw[:, 0].astype(np.int64) * hw[:, 1]).astype(np.uint32), np.arange(O + 1, dtype=np.int64), hw)
+    lib = capi.load()
+    with torch.cuda.device(dev):
+        stream = capi.current_stream(dev)
+        table = torch.from_numpy(np.concatenate([part_off, obj_off, hw.reshape(-1).view(np.int64),
+                                                 xy.view(np.int64)])).to(dev)          # one upload
+        part_off_d, obj_off_d = table[:P + 1], table[P + 1:P + O + 2]
+        hw_d = table[P + O + 2:P + 2 * O + 2].view(torch.int32)
+        xy_d = table[P + 2 * O + 2:].view(torch.float64)
+        edge_pts = torch.empty(V, dtype=torch.int64, device=dev)
+        capi.check('bgs_poly_rle_edge_points',
+                   lib.bgs_poly_rle_edge_points(capi.ptr(xy_d), capi.ptr(part_off_d), _np_ptr(part_off), V, P,
+                                                capi.ptr(edge_pts), stream))
+        pt_off = _scan0(edge_pts)
+        geom = (capi.ptr(xy_d), capi.ptr(part_off_d), capi.ptr(obj_off_d), capi.ptr(hw_d), V, P, O, capi.ptr(pt_off))
+        tally = torch.zeros(P, dtype=torch.int32, device=dev)
+        capi.check('bgs_poly_rle_crossings', lib.bgs_poly_rle_crossings(*geom, None, 0, capi.ptr(tally), None, stream))
+        cross_off = _scan0(tally)
+        C = int(cross_off[-1].item())                      # the one synchronisation: sizes every buffer below
+        if C > RLE_MAX_AREA:
+            raise ValueError('poly_rle: %d boundary crossings in one call; split the batch' % C)
+        keys = torch.empty(max(C, 1), dtype=torch.int32, device=dev)
+        trans = torch.empty(max(C, 1), dtype=torch.int32, device=dev)
+        events = torch.empty(max(C, 1), dtype=torch.int32, device=dev)
+        cursor = torch.zeros(P, dtype=torch.int32, device=dev)
+        capi.check('bgs_poly_rle_crossings',
+                   lib.bgs_poly_rle_crossings(*geom, capi.ptr(cross_off), C, capi.ptr(cursor), capi.ptr(keys), stream))
+        tcnt = torch.empty(P, dtype=torch.int32, device=dev)
+        capi.check('bgs_poly_rle_resolve',
+                   lib.bgs_poly_rle_resolve(capi.ptr(keys), capi.ptr(cross_off), None, P, _RLE_PARITY, None, None,
+                                            capi.ptr(hw_d), capi.ptr(obj_off_d), O, C, capi.ptr(trans),
+                                            capi.ptr(tcnt), None, stream))
+        ev_off = _scan0(tcnt)
+        capi.check('bgs_poly_rle_events_from_transitions',
+                   lib.bgs_poly_rle_events_from_transitions(capi.ptr(trans), capi.ptr(cross_off), capi.ptr(tcnt),
+                                                            capi.ptr(ev_off), P, C, capi.ptr(events), stream))
+        merged, mcnt = keys, torch.empty(O, dtype=torch.int32, device=dev)      # (the keys are spent: reuse)
+        runs = torch.empty(O, dtype=torch.int32, device=dev)
+        capi.check('bgs_poly_rle_resolve',
+                   lib.bgs_poly_rle_resolve(capi.ptr(events), capi.ptr(ev_off), capi.ptr(obj_off_d), O, _RLE_UNION,
+                                            capi.ptr(obj_off_d), None, capi.ptr(hw_d), None, 0, C, capi.ptr(merged),
+                                            capi.ptr(mcnt), capi.ptr(runs), stream))
+
+        def write(out_off, out):
+            capi.check('bgs_poly_rle_write',
+                       lib.bgs_poly_rle_write(capi.ptr(merged), capi.ptr(ev_off), capi.ptr(obj_off_d), capi.ptr(mcnt),
+                                              O, capi.ptr(obj_off_d), None, None, capi.ptr(hw_d), C,
+                                              capi.ptr(out_off), C + O, capi.ptr(out), stream))
+        counts, offsets = _rle_finish(lib, O, C + O, dev, runs, write)
+    return counts, offsets, hw
+
+
+def poly_rle(objects, sizes, device=None):
+    """:func:`poly_rle_counts` as RLE dicts: a list of ``O`` ``{'size': [h, w], 'counts': bytes}``, what
+    ``mask.merge(mask.frPyObjects(parts, h, w))`` returns for every object."""
+    from . import rle
+    counts, offsets, hw = poly_rle_counts(objects, sizes, device)
+    strings = rle.pack_strings(counts, offsets)
+    sz = hw.tolist()
+    return [{'size': sz[k], 'counts': strings[k]} for k in range(len(strings))]
+
+
+def rle_merge_counts(counts, list_off, grp_off, sizes, intersect=False, device=None):
+    """``rleMerge`` for ``G`` groups of run lists at once (stage B of csrc/poly_rle.hip): list ``l`` owns
+    ``counts[list_off[l] : list_off[l + 1]]`` (uint32, host), group ``g`` owns lists ``grp_off[g] .. grp_off[g + 1]``
+    (at least one), ``sizes`` ``[G, 2]`` (h, w).  Returns ``(counts uint32, offsets int64 [G + 1])`` on the host: the
+    canonical run list of every union (intersection); a group of one list comes back unchanged.  Three launches, no
+    host read before the copy back."""
+    import numpy as np
+    counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    list_off = np.ascontiguousarray(list_off, dtype=np.int64).reshape(-1)
+    grp_off = np.ascontiguousarray(grp_off, dtype=np.int64).reshape(-1)
+    hw = np.ascontiguousarray(np.asarray(sizes, dtype=np.int64).reshape(-1, 2))
+    G, L, R = grp_off.size - 1, list_off.size - 1, counts.size
+    if G < 0 or L < 0 or hw.shape[0] != G:
+        raise ValueError('rle_merge: offsets must be [n + 1] and sizes [G, 2]')
+    if G == 0:
+        return np.zeros(0, np.uint32), np.zeros(1, np.int64)
+    if grp_off[0] != 0 or grp_off[-1] != L or (np.diff(grp_off) <= 0).any():
+        raise ValueError('rle_merge: every group needs at least one mask')
+    if list_off[0] != 0 or list_off[-1] != R or (np.diff(list_off) <= 0).any():
+        raise ValueError('rle_merge: an RLE without runs')
+    area = hw[:, 0] * hw[:, 1]
+    if hw.min() <= 0 or area.max() > RLE_MAX_AREA:
+        raise ValueError('rle_merge: sizes must be positive with h * w <= 2^31 - 1')
+    sums = np.add.reduceat(counts.astype(np.int64), list_off[:-1])
+    if (sums != np.repeat(area, np.diff(grp_off))).any():
+        raise ValueError('rle_merge: the runs of a mask do not cover h * w pixels')
+    dev = _rle_device(device, 'rle_merge')
+    lib = capi.load()
+    ev_base = list_off[grp_off] - grp_off
+    E = R - L
+    with torch.cuda.device(dev):
+        stream = capi.current_stream(dev)
+        table = torch.from_numpy(np.concatenate([list_off, grp_off, ev_base,
+                                                 hw.astype(np.int32).reshape(-1).view(np.int64)])).to(dev)
+        list_off_d, grp_off_d = table[:L + 1], table[L + 1:L + G + 2]
+        ev_base_d = table[L + G + 2:L + 2 * G + 3]
+        hw_d = table[L + 2 * G + 3:].view(torch.int32)
+        counts_d = torch.from_numpy(counts.view(np.int32)).to(dev)
+        cum = torch.cumsum(counts_d, 0, dtype=torch.int64)
+        events = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
+        trans = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
+        capi.check('bgs_poly_rle_events_from_runs',
+                   lib.bgs_poly_rle_events_from_runs(capi.ptr(cum), capi.ptr(list_off_d), _np_ptr(list_off), L, R,
+                                                     capi.ptr(events), stream))
+        tcnt = torch.empty(G, dtype=torch.int32, device=dev)
+        runs = torch.empty(G, dtype=torch.int32, device=dev)
+        mode = _RLE_INTERSECT if intersect else _RLE_UNION
+        capi.check('bgs_poly_rle_resolve',
+                   lib.bgs_poly_rle_resolve(capi.ptr(events), capi.ptr(ev_base_d), None, G, mode, capi.ptr(grp_off_d),
+                                            capi.ptr(list_off_d), capi.ptr(hw_d), None, 0, E, capi.ptr(trans),
+                                            capi.ptr(tcnt), capi.ptr(runs), stream))
+
+        def write(out_off, out):
+            capi.check('bgs_poly_rle_write',
+                       lib.bgs_poly_rle_write(capi.ptr(trans), capi.ptr(ev_base_d), None, capi.ptr(tcnt), G,
+                                              capi.ptr(grp_off_d), capi.ptr(list_off_d), capi.ptr(counts_d),
+                                              capi.ptr(hw_d), E, capi.ptr(out_off), R + G, capi.ptr(out), stream))
+        return _rle_finish(lib, G, R + G, dev, runs, write)
+
+
+def rle_merge(groups, intersect=False, device=None):
+    """``pycocotools.mask.merge`` for many groups at once: ``groups`` is a list of lists of RLE dicts (``counts`` a
+    compressed ``bytes`` / ``str`` or a list of ints); returns one ``{'size', 'counts': bytes}`` per group.  Masks of
+    different sizes in one group are a ``ValueError``."""
+    import numpy as np
+    from . import rle
+    from .lvis_eval import _rle_tables
+    groups = [list(g) for g in groups]
+    if not groups:
+        return []
+    if any(len(g) == 0 for g in groups):
+        raise ValueError('rle_merge: every group needs at least one mask')
+    flat = [r for g in groups for r in g]
+    if any(not isinstance(r, dict) for r in flat):
+        raise ValueError('rle_merge: the masks are RLE dicts (polygons go through poly_rle)')
+    counts, list_off, sz = _rle_tables(flat, 'rle_merge')
+    grp_off = np.zeros(len(groups) + 1, np.int64)
+    np.cumsum([len(g) for g in groups], out=grp_off[1:])
+    first = sz[grp_off[:-1]]
+    if (sz != np.repeat(first, np.diff(grp_off), axis=0)).any():
+        raise ValueError('rle_merge: masks of different sizes in one group')
+    out, off = rle_merge_counts(counts, list_off, grp_off, first, intersect, device)
+    strings = rle.pack_strings(out, off)
+    sizes = first.tolist()
+    return [{'size': sizes[g], 'counts': strings[g]} for g in range(len(strings))]
+
+
+# ----------------------------------------------------------------------------------------
 # LVIS evaluation  (lvis-api/lvis/eval.py:116-292; csrc/lvis_eval.hip)
 # ----------------------------------------------------------------------------------------
 class LvisProblems(object):

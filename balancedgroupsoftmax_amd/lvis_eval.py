@@ -12,7 +12,12 @@ matchings (``functional.lvis_match``), one launch each, and sends back ten match
 range, detection); the host accumulates precision / recall per category in float64.  Match tables and
 precision / recall equal the reference's exactly (tests/golden/make_golden_lvis_eval.py executes it).
 
-Not supported: polygon ground truths under ``iou_type='segm'`` (``rleFrPoly``), the proposal evaluations.
+Polygon ground truths (every LVIS annotation is one) become RLE on the device, all in one batch:
+``LVISGroundTruth.rasterize_polygons()`` or ``lvis_eval(..., rasterize=True)`` (``functional.poly_rle``,
+csrc/poly_rle.hip: a restatement of pycocotools' ``rleFrPoly`` / ``rleMerge``, see tests/poly_rle_ref.py).  Without
+that step ``LVISEval(..., 'segm')`` refuses a polygon, as before.
+
+Not supported: the proposal evaluations.
 """
 import json
 from collections import OrderedDict, defaultdict
@@ -143,6 +148,57 @@ class LVISGroundTruth(object):
     def load_imgs(self, ids=None):
         return self._load(self.imgs, ids)
 
+    # ---- polygons and uncompressed RLEs -> RLE (lvis.py:222-258)
+    def _size_of(self, ann):
+        img = self.imgs[ann['image_id']]
+        return int(img['height']), int(img['width'])
+
+    def ann_to_rle(self, ann, device=None):
+        """``LVIS.ann_to_rle``: a polygon annotation (a list of parts) is rasterised part by part and merged, an
+        uncompressed RLE (``counts`` a list) is compressed, an RLE is returned as it is.  One annotation per call;
+        :meth:`rasterize_polygons` converts a whole file in one device batch."""
+        from . import functional as BF
+        from . import rle
+        segm = ann['segmentation']
+        if isinstance(segm, list):
+            return BF.poly_rle([segm], self._size_of(ann), device)[0]
+        if isinstance(segm['counts'], list):
+            return {'size': [int(segm['size'][0]), int(segm['size'][1])],
+                    'counts': rle.counts_to_string(segm['counts'])}
+        return segm
+
+    def ann_to_mask(self, ann, device=None):
+        """``LVIS.ann_to_mask``: the annotation's binary mask, uint8 ``[h, w]``."""
+        from . import rle
+        return rle.decode(self.ann_to_rle(ann, device))
+
+    def rasterize_polygons(self, device=None):
+        """Replaces, IN PLACE, every polygon ``'segmentation'`` of the file by its RLE at the image's size (all
+        polygons of all annotations in one device batch: ``functional.poly_rle``) and every uncompressed RLE by its
+        compressed form; RLEs stay.  Returns how many annotations it converted.  After it,
+        ``LVISEval(gt, results, 'segm')`` runs."""
+        from . import functional as BF
+        from . import rle
+        anns = self.dataset['annotations']
+        poly = [a for a in anns if isinstance(a.get('segmentation'), list)]
+        plain = [a for a in anns if isinstance(a.get('segmentation'), dict)
+                 and isinstance(a['segmentation']['counts'], list)]
+        if poly:
+            rles = BF.poly_rle([a['segmentation'] for a in poly], [self._size_of(a) for a in poly], device)
+            for a, r in zip(poly, rles):
+                a['segmentation'] = r
+        if plain:
+            counts = [np.asarray(a['segmentation']['counts'], dtype=np.int64).reshape(-1) for a in plain]
+            flat = np.concatenate(counts) if counts else np.zeros(0, np.int64)
+            if flat.size and (flat.min() < 0 or flat.max() > 0xffffffff):
+                raise ValueError('rasterize_polygons: run lengths must fit in 32 bits')
+            off = np.zeros(len(counts) + 1, np.int64)
+            np.cumsum([c.size for c in counts], out=off[1:])
+            strings = rle.pack_strings(flat.astype(np.uint32), off)
+            for a, s in zip(plain, strings):
+                a['segmentation'] = {'size': [int(v) for v in a['segmentation']['size']], 'counts': s}
+        return len(poly) + len(plain)
+
 
 class Params(object):
     def __init__(self, iou_type, max_dets=300):
@@ -170,8 +226,9 @@ def _rle_tables(segms, what):
     strings, where, plain = [], [], {}
     for k, s in enumerate(segms):
         if isinstance(s, (list, tuple)):
-            raise NotImplementedError('%s: polygon segmentations are not supported (no rleFrPoly here); '
-                                      'give the masks as RLE' % what)
+            raise NotImplementedError('%s: polygon segmentations are not converted here; give the masks as RLE '
+                                      '(LVISGroundTruth.rasterize_polygons() or lvis_eval(..., rasterize=True) '
+                                      'converts a ground-truth file on the device)' % what)
         sizes[k] = s['size']
         c = s['counts']
         if isinstance(c, str):
@@ -584,11 +641,12 @@ class LVISEval(object):
             print(line)
 
 
-def lvis_eval(results_or_files, result_types, gt, max_dets=300, device=None):
+def lvis_eval(results_or_files, result_types, gt, max_dets=300, device=None, rasterize=False):
     """The reference's wrapper (lvis_utils.py:16-54): for every type in ``result_types`` ('bbox', 'segm') evaluate
     ``results_or_files[type]`` (a list of result dicts or the path of a json file: either value of ``results2json``)
     against ``gt`` (an :class:`LVISGroundTruth`, a dataset dict or a path), print the table, and return ``{type:
-    results}``."""
+    results}``.  ``rasterize=True`` first converts the ground truth's polygons to RLE on the device, in place
+    (:meth:`LVISGroundTruth.rasterize_polygons`): an LVIS json goes in as it is distributed."""
     for t in result_types:
         if t in ('proposal', 'proposal_fast', 'proposal_fast_percat'):
             raise NotImplementedError("lvis_eval: result type '%s' (proposal recall) is not implemented" % t)
@@ -596,6 +654,8 @@ def lvis_eval(results_or_files, result_types, gt, max_dets=300, device=None):
             raise ValueError("lvis_eval: unknown result type '%s'" % (t,))
     if not isinstance(gt, LVISGroundTruth):
         gt = LVISGroundTruth(gt)
+    if rasterize:
+        gt.rasterize_polygons(device)
     out = OrderedDict()
     for t in result_types:
         ev = LVISEval(gt, results_or_files[t], t, max_dets=max_dets, device=device)

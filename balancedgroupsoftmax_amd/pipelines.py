@@ -402,7 +402,8 @@ class TrainPipeline(_DevicePipeline):
     the padded tensors.  The nearest-neighbour rule of those two is OpenCV's ``INTER_NEAREST`` as published; like the
     bilinear rule of the image it is not pinned against an executed cv2.
 
-    Out of scope: polygon masks (convert them to RLE once, offline), datasets / samplers / loaders, ``RandomCrop``
+    Polygon masks are not taken by ``prepare``; :meth:`poly2mask` converts them to RLE on the device first (or once,
+    offline: tools/lvis_polygons_to_rle.py).  Out of scope: datasets / samplers / loaders, ``RandomCrop``
     and the photometric transforms, ``keep_ratio=False``, ``LoadProposals``."""
 
     def __init__(self, img_scale, multiscale_mode='range', ratio_range=None, flip_ratio=None, mean=(0., 0., 0.),
@@ -579,8 +580,9 @@ class TrainPipeline(_DevicePipeline):
                     raise ValueError('sample %d: Collect asks for gt_masks, the sample has none' % i)
                 if isinstance(m, (list, tuple)):
                     if any(isinstance(e, (list, tuple)) for e in m):
-                        raise NotImplementedError('sample %d: polygon masks are not supported (convert them to COCO '
-                                                  'RLE once, offline)' % i)
+                        raise NotImplementedError('sample %d: polygon masks are not supported here (convert them to '
+                                                  'COCO RLE first: TrainPipeline.poly2mask(samples), or once, '
+                                                  'offline)' % i)
                     if not all(isinstance(e, dict) and 'counts' in e and 'size' in e for e in m):
                         raise TypeError('sample %d: gt_masks is a uint8 [G, h, w] array or a list of COCO RLE dicts'
                                         % i)
@@ -600,6 +602,39 @@ class TrainPipeline(_DevicePipeline):
                     raise ValueError('sample %d: Collect asks for gt_semantic_seg, the sample has none' % i)
                 if g.dtype not in (np.uint8, torch.uint8) or len(g.shape) != 2:
                     raise TypeError('sample %d: gt_semantic_seg is uint8 [h, w]' % i)
+
+    # -- polygons -> RLE (LoadAnnotations._poly2mask, loading.py:69-82) ------------------------
+    @staticmethod
+    def poly2mask(samples, device=None):
+        """``LoadAnnotations(poly2mask=True)`` up to the RLE: returns shallow COPIES of the samples whose polygon
+        ``gt_masks`` (a list of G entries, each a list of parts ``[x0, y0, x1, y1, ...]``) are COCO RLE dicts at the
+        image's ``(h, w)`` — what :meth:`prepare` takes.  Entries that already are RLE dicts pass through (an
+        uncompressed one as it is: ``prepare`` reads it), dense arrays too.  The polygons of ALL samples go through
+        one device batch (``functional.poly_rle``, csrc/poly_rle.hip).  Unlike ``prepare`` this call WAITS for the
+        device, once: for the read that sizes the result and the copy back of the run lengths."""
+        from . import functional as BF
+        items = [samples] if isinstance(samples, dict) else list(samples)
+        out = [dict(s) for s in items]
+        objects, sizes, where = [], [], []
+        for i, s in enumerate(out):
+            m = s.get('gt_masks')
+            if not isinstance(m, (list, tuple)):
+                continue
+            if not any(isinstance(e, (list, tuple)) for e in m):
+                continue
+            img = imread(s['img']) if isinstance(s['img'], str) else s['img']
+            h, w = int(img.shape[0]), int(img.shape[1])
+            s['gt_masks'] = m = list(m)
+            for g, e in enumerate(m):
+                if isinstance(e, (list, tuple)):
+                    objects.append(e)
+                    sizes.append((h, w))
+                    where.append((i, g))
+        if objects:
+            rles = BF.poly_rle(objects, sizes, device)
+            for (i, g), r in zip(where, rles):
+                out[i]['gt_masks'][g] = r
+        return out[0] if isinstance(samples, dict) else out
 
     # -- sources of the masks ----------------------------------------------------------------
     @staticmethod

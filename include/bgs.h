@@ -1047,6 +1047,64 @@ int bgs_lvis_match(const double* ious, const long long* dt_off, const long long*
                    const double* host_iou_thrs, int T, void* workspace, size_t workspace_bytes, int* dt_match,
                    uint8_t* dt_ignore, unsigned* dt_bits, uint8_t* gt_ignore_out, bgs_stream_t stream);
 
+/* Polygon ground truths as COCO run lengths (csrc/poly_rle.hip): rleFrPoly + rleMerge of pycocotools' maskApi.c
+ * (mask.frPyObjects then mask.merge, as LoadAnnotations._poly2mask and LVIS.ann_to_rle call them) for all objects of a
+ * batch, in a number of launches that does not depend on the batch.  The arithmetic contract is the restatement in
+ * tests/poly_rle_ref.py (pycocotools itself is not a dependency and was never executed): doubles, one rounding per
+ * operation.  Object o owns parts obj_off[o] .. obj_off[o + 1], part p owns vertices part_off[p] .. part_off[p + 1]
+ * (at least one) of xy [V, 2] fp64 (x, y); sizes [O, 2] int32 (h, w) with h * w <= 2^31 - 1 (the caller's check);
+ * every offset table is device int64, the host_* copies are validated on the host (begin at 0, strictly increasing,
+ * end at the item count: BGS_ERR_INVALID_ARG otherwise).  Coordinates beyond +-1e6 are clamped (callers refuse them).
+ *   A "transition" is a column-major position x * h + y < h * w at which the mask value changes; the counts are the
+ *   differences of consecutive transitions from 0 to h * w (first run = zeros, 0 when position 0 is a transition).
+ * Stage A
+ *   bgs_poly_rle_edge_points: edge_pts [V] int64 = max(dx, dy) + 1 boundary points of the edge that starts at every
+ *     vertex.  The caller scans them: pt_off [V + 1] int64, pt_off[0] = 0.
+ *   bgs_poly_rle_crossings: keys == NULL counts the crossings of every part into tally [P] int32 (zero on entry); the
+ *     caller scans the tallies into cross_off [P + 1] and reads cross_off[P] = capacity ONCE.  keys != NULL writes
+ *     key = 2 * position of every crossing into keys [capacity] uint32 at cross_off[p] + (a slot from tally [P], zero
+ *     on entry).  The order of a part's keys is arbitrary; bgs_poly_rle_resolve sorts them.
+ * Stage B (also for run lists that did not come from stage A)
+ *   bgs_poly_rle_resolve: segment s owns keys[base[i0] : base[i1]] with (i0, i1) = (ind[s], ind[s + 1]) or
+ *     (s, s + 1) when ind is NULL.  key = 2 * position + (1 for a falling edge).  The keys are sorted IN PLACE (no
+ *     cap on the length), the positions at which the value changes go to trans[base[i0] + 0 ..] (ascending), their
+ *     number to tcnt [S], and, when runs is not NULL, the length of the run list to runs [S] (tcnt + 1).  mode:
+ *     BGS_RLE_PARITY (value = an odd number of keys so far: the crossings of one part), BGS_RLE_UNION (value = more
+ *     risen than fallen), BGS_RLE_INTERSECT (value = all nl_off[s + 1] - nl_off[s] lists risen).  sizes [., 2] int32:
+ *     row s, or, with owner_off [n_owner + 1], the row whose range of owner_off holds s.  copy_off: see write.
+ *     trans must not alias keys.
+ *   bgs_poly_rle_events_from_transitions: transition j of segment s (trans[seg_off[s] + j], j < tcnt[s]) becomes
+ *     events[ev_off[s] + j] = 2 * position + (j & 1); ev_off [S + 1] = the exclusive scan of tcnt.
+ *   bgs_poly_rle_events_from_runs: cum [R] int64 = the inclusive scan of all run lengths; run j of list l (runs
+ *     list_off[l] .. list_off[l + 1]) other than its last becomes events[i - l] (i its global index) = 2 * (the
+ *     list's prefix sum) + (j & 1): the events of lists l0 .. l1 are events[list_off[l0] - l0 : list_off[l1] - l1].
+ *   bgs_poly_rle_write: out[out_off[s] + r] = transition r - transition r - 1 (0 before the first, h * w after the
+ *     last); out_off [S + 1] = the exclusive scan of runs.  With copy_off (= list_off) and src_counts, a segment with
+ *     exactly one list (nl_off) receives that list's runs unchanged, as rleMerge returns them.  No store lands outside
+ *     [0, out_capacity).
+ * Zero items (S, P, V == 0) is BGS_OK. */
+#define BGS_RLE_PARITY 0
+#define BGS_RLE_UNION 1
+#define BGS_RLE_INTERSECT 2
+int bgs_poly_rle_edge_points(const double* xy, const long long* part_off, const long long* host_part_off,
+                             long long V, int P, long long* edge_pts, bgs_stream_t stream);
+int bgs_poly_rle_crossings(const double* xy, const long long* part_off, const long long* obj_off, const int* sizes,
+                           long long V, int P, int O, const long long* pt_off, const long long* cross_off,
+                           long long capacity, int* tally, unsigned* keys, bgs_stream_t stream);
+int bgs_poly_rle_events_from_transitions(const unsigned* trans, const long long* seg_off, const int* tcnt,
+                                         const long long* ev_off, int S, long long capacity, unsigned* events,
+                                         bgs_stream_t stream);
+int bgs_poly_rle_events_from_runs(const long long* cum, const long long* list_off, const long long* host_list_off,
+                                  int L, long long R, unsigned* events, bgs_stream_t stream);
+int bgs_poly_rle_resolve(unsigned* keys, const long long* base, const long long* ind, int S, int mode,
+                         const long long* nl_off, const long long* copy_off, const int* sizes,
+                         const long long* owner_off, int n_owner, long long capacity, unsigned* trans, int* tcnt,
+                         int* runs, bgs_stream_t stream);
+int bgs_poly_rle_write(const unsigned* trans, const long long* base, const long long* ind, const int* tcnt, int S,
+                       const long long* nl_off, const long long* copy_off, const unsigned* src_counts,
+                       const int* sizes, long long capacity, const long long* out_off, long long out_capacity,
+                       unsigned* out, bgs_stream_t stream);
+
 /* Gradient clipping + SGD update of ALL trainable tensors (csrc/optim.hip): the reference's optimizer hook
  * `DistOptimizerHook.after_train_iter` (mmdet/core/utils/dist_utils.py:51-58): `clip_grads` (max_norm = 35, L2:
  * torch.nn.utils.clip_grad_norm_) -> `optimizer.step()` (torch.optim.SGD with momentum and weight decay,
