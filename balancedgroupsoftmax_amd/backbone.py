@@ -237,7 +237,14 @@ class Bottleneck(nn.Module):
             fk.join()
         return BF.conv2d_nhwc(out, f['c3'][0], f['c3'][1], relu=True, residual=identity)
 
-    def run(self, x, f):
+    def run(self, x, f, next_c1=None, h=None):
+        """The block on ``x``.  ``next_c1``: folded ``(filter, bias)`` of the NEXT block's conv1 — where this block's
+        tail launch can emit it too (``BF.fused_c3_next_eligible``: a frozen layer1 block in front of a frozen 1x1 /
+        stride-1 conv1) the result is ``(y, h)`` with ``h`` = that conv1's output; everywhere else ``y`` alone, as
+        without it.  ``h``: THIS block's conv1 output, computed by the previous block's launch — conv1 is skipped."""
+        if h is not None and (x.dtype == torch.bfloat16 or self.groups > 1 or self.with_dcn or
+                              (torch.is_grad_enabled() and x.requires_grad)):
+            raise RuntimeError('Bottleneck.run: a precomputed conv1 output is for the frozen fp32 block only')
         if x.dtype == torch.bfloat16:
             return self.run_bf16_storage(x, f)
         # Residual fork (x feeds conv1 / the projection shortcut AND the identity path): with a trainable
@@ -286,15 +293,24 @@ class Bottleneck(nn.Module):
             if fk is not None:
                 fk.join()
             return BF.conv2d_autograd(out, f['c3'][0], f['c3'][1], relu=out_relu, residual=identity)
-        out = BF.conv2d_autograd(xin, f['c1'][0], f['c1'][1], relu='consumers', mask_input=first_mask,
-                                 passthrough=first_pt)
-        if first_pt:
-            out, identity = out
+        if h is not None:
+            out = h                                # (= relu(conv1(x)), bit for bit: the previous block's tail launch)
+        else:
+            out = BF.conv2d_autograd(xin, f['c1'][0], f['c1'][1], relu='consumers', mask_input=first_mask,
+                                     passthrough=first_pt)
+            if first_pt:
+                out, identity = out
         if not fuse and BF.fused_c3_eligible(out, f['c2'][0], f['c3'][0], self.stride, identity):
             # frozen 64 -> 64 -> 256 block on a large map (ResNet-50 layer1): conv2 -> conv3 + residual + ReLU in one
             # launch, the 64-channel intermediate stays in LDS (csrc/conv_bfx.hip, round 6; bit-identical)
             if fk is not None:
                 fk.join()
+            if next_c1 is not None and BF.fused_c3_next_eligible(out, f['c2'][0], f['c3'][0], self.stride, identity,
+                                                                 next_c1[0], next_c1[1]):
+                # ... and the next block's frozen conv1 in its epilogue: the workgroup holds all 256 channels of its
+                # pixels (csrc/bottleneck_tail_planes.hip, NEXT form; bit-identical) -> (y, h)
+                return BF.conv3x3_c3_next_fused_nhwc(out, f['c2'][0], f['c2'][1], f['c3'][0], f['c3'][1], next_c1[0],
+                                                     next_c1[1], residual=identity, relu3=True)
             return BF.conv3x3_c3_fused_nhwc(out, f['c2'][0], f['c2'][1], f['c3'][0], f['c3'][1], residual=identity,
                                             relu3=True)
         out = BF.conv2d_autograd(out, f['c2'][0], f['c2'][1], stride=self.stride, pad=1,
@@ -416,9 +432,23 @@ class ResNet(nn.Module):
         if first < 0:
             x = self._forward_stem(x)
             first = 0
-        for i in range(first, last + 1):
-            for blk in getattr(self, self.res_layers[i]):
-                x = blk.run(x, blk.folded())
+        # the chain of blocks of THIS piece: a block may hand the next one its conv1 output (Bottleneck.run); that second
+        # tensor never crosses a piece boundary (the pieces run on different streams)
+        chain = [(i, blk) for i in range(first, last + 1) for blk in getattr(self, self.res_layers[i])]
+        h, f = None, None
+        for k, (i, blk) in enumerate(chain):
+            nxt = chain[k + 1][1] if k + 1 < len(chain) else None
+            fn = None
+            # (only behind a 64-wide stride-1 block — layer1 — and in front of a frozen plain block: the one case
+            #  BF.fused_c3_next_eligible accepts; a trained block's fold is on the tape and is built once, by its own run)
+            if nxt is not None and blk.width == 64 and blk.stride == 1 and blk.groups == 1 and not blk.with_dcn \
+                    and nxt.groups == 1 and not nxt.with_dcn and not _trainable(nxt):
+                fn = nxt.folded()
+            r = blk.run(x, f if f is not None else blk.folded(), next_c1=None if fn is None else fn['c1'], h=h)
+            x, h = r if isinstance(r, tuple) else (r, None)
+            f = fn
+            if k + 1 < len(chain) and chain[k + 1][0] == i:
+                continue
             if i in self.out_indices:
                 # a trainable stage hands on a `relu='consumers'` tensor (its ReLU backward rides in the
                 # next block's dgrad epilogue); what LEAVES the trunk is an ordinary tensor any consumer

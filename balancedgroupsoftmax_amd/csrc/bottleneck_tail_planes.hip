@@ -14,6 +14,21 @@
 //   * conv3: wave w owns 64 pixels x channels 64 w .. (acc[2][2]), four k steps, filter fragments from L2;
 //   * epilogue in two halves of 32 pixels through the LDS transpose: bias3, then the residual, then the clamp.
 // LDS 46 KB (the patch planes; every later stage overlays them): three workgroups per CU.
+//
+// NEXT = 64 | 128: the NEXT block's conv1 (1x1 / stride 1, 256 -> NEXT, folded BN, ReLU) in the epilogue.  The workgroup
+// holds all 256 output channels of its 64 pixels and a 1x1 conv needs no halo.  The threads keep the final fp32 values of
+// both epilogue halves in registers (exactly what they store to y, which the next block still needs as its residual), then:
+//   * those values are split (the same split3) into A planes in LDS, [plane][k step][pixel][32 B], in two K chunks of 128
+//     channels x all 64 pixels (48.75 KB; the k steps 32 B further apart than their 2 KB: the lanes that hold one pixel
+//     write 8 k steps at once).  A lane holds 4 channels, so a chunk lives in one half of the lanes: the halves trade
+//     registers first (v_permlane32_swap) and every lane splits and writes in both chunks;
+//   * every 32 x 32 output tile belongs to ONE wave for its whole reduction — NEXT = 128: wave w owns 64 pixels x channels
+//     32 w .. (two tiles on one filter fragment); NEXT = 64: wave (wm, wn) owns 32 pixels x 32 channels — 16 k steps
+//     ascending, the six plane products of a step in the ring kernel's order, filter fragments from L2 two steps ahead:
+//     the summation order of conv1x1_planes_bfx_kernel / conv1x1_bfx_wide_kernel / the operand ring, hence BIT-IDENTICAL
+//     to the launch it replaces.  No accumulator changes hands and no K range is split;
+//   * bias, ReLU and 16-byte stores of h [N,H,W,NEXT] through the LDS transpose.
+// LDS 48.75 KB, <= 156 VGPRs: still three workgroups per CU.  NEXT = 0 is the kernel above, instruction for instruction.
 #include <stdlib.h>
 
 #include "conv_args.h"
@@ -56,14 +71,33 @@ struct TailArgs {
   int tiles_y, tiles_x, tiles, chunk;
 };
 
+struct TailNextArgs {
+  TailArgs t;
+  const __bf16* ws1n;    // split filter of the next block's conv1 [3][16][NEXT][16]
+  const float* bias1n;   // [NEXT] or null
+  float* h;              // [N,H,W,NEXT]
+};
+template <int NEXT> struct TailArgsOf { typedef TailNextArgs type; };
+template <> struct TailArgsOf<0> { typedef TailArgs type; };
+__device__ __forceinline__ const TailArgs& tail_base(const TailArgs& a) { return a; }
+__device__ __forceinline__ const TailArgs& tail_base(const TailNextArgs& a) { return a.t; }
+
 constexpr int kOob = 0x7f000000;   // byte offset past every descriptor this kernel builds: the load returns 0
 
-__global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(TailArgs g) {
+template <int NEXT>
+__global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typename TailArgsOf<NEXT>::type ga) {
+  static_assert(NEXT == 0 || NEXT == 64 || NEXT == 128, "width of the next block's conv1");
+  const TailArgs& g = tail_base(ga);
   constexpr int NS = 3, CM = 64, CO3 = 256, KC2 = 36, KC3 = 4;
   constexpr int PW = 10, PS = 12, PSLOTS = PW * PS;                 // 10 x 10 patch in rows of 12 slots
   constexpr int AQ = PW * PW * 16, AQT = (AQ + kThreads - 1) / kThreads;   // 1600 fp32 quads: 7 per thread (the 7th: 64 threads)
   constexpr int KS = PSLOTS * 32, PL = 4 * KS;                      // 3840 B per k step, 15,360 per plane
-  constexpr int LDS_BYTES = NS * PL;                                // 46,080
+  // conv1' A planes (NEXT > 0), one 128-deep K chunk of the 64 pixels at a time: 8 k steps of 2 KB + 32 B (the lanes
+  // that hold one pixel write 8 k steps at once), 16,640 per plane, 49,920 in all
+  constexpr int KCN = CO3 / 16, KCH = KCN / 2, KSN = 64 * 32 + 32, PLN = KCH * KSN;
+  constexpr int LDS_BYTES = NEXT ? NS * PLN : NS * PL;              // 46,080 (NEXT > 0: 49,920)
+  static_assert(64 * (NEXT + 8) * 4 <= LDS_BYTES, "the h transpose tile overlays the planes");
+  static_assert(NS * PL <= LDS_BYTES && 3 * LDS_BYTES <= 160 * 1024, "three workgroups per CU");
   constexpr int LD2 = CM + 4, S2_BYTES = 64 * LD2 * 4;              // conv2 transpose tile: 17,408 at offset 0
   constexpr int Y_OFF = 18 * 1024;                                  // conv3's A planes behind it: 18,432 .. 43,008
   constexpr int P3_CH = 64 * 32, P3_PL = KC3 * P3_CH;               // 2 KB per k step, 8 KB per plane
@@ -249,6 +283,7 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(Tai
   const __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(g.res ? g.res : g.x), 0, g.res ? out_bytes : 0, 0x00020000);     // 0 bytes: every read is 0
   const __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(g.y, 0, out_bytes, 0x00020000);
+  f32x4 vn[NEXT ? 2 : 1][NEXT ? 8 : 1];                             // (NEXT > 0) this thread's final values, both halves
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
     f32x4 rs[8];
@@ -280,8 +315,119 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(Tai
       }
       if (ho < g.H && wo < g.W)
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, (((n * g.H + ho) * g.W + wo) * CO3 + e4) * 4, 0, 0);
+      if constexpr (NEXT > 0) vn[a][ps] = v;
     }
     __syncthreads();
+  }
+
+  if constexpr (NEXT > 0) {
+    // ---- phase 5: the next block's conv1 on the 64 pixels x 256 channels this workgroup has just stored.  Every 32 x 32
+    // output tile is reduced by ONE wave, k steps ascending.  NEXT = 128: wave w owns all 64 pixels x channels 32 w .. (two
+    // tiles: a filter fragment from L2 serves both); NEXT = 64: wave (wm, wn) owns pixels 32 wm .. x channels 32 wn ...
+    constexpr int LDH = NEXT + 8, NA = NEXT == 128 ? 2 : 1;
+    const int a0 = NEXT == 128 ? 0 : (wave >> 1);
+    const int tn = NEXT == 128 ? wave : (wave & 1);
+    const __amdgpu_buffer_rsrc_t bn_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<__bf16*>(ga.ws1n), 0, NS * KCN * NEXT * 32, 0x00020000);
+    const int bn_lane = ((tn * 32 + frow) * 16 + fk * 8) * 2;       // bytes
+    auto load_bn = [&](int kc, bf16x8 (&dst)[NS]) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s)
+        dst[s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(bn_rsrc, bn_lane, (s * KCN + kc) * NEXT * 32, 0));
+    };
+    bf16x8 fn[3][NS];                                               // two k steps ahead (an L2 round trip > one step's MFMAs)
+    load_bn(0, fn[0]);                                              // travels under the staging
+    load_bn(1, fn[1]);
+    // A thread holds 4 channels (lane: channels 4 lane ..) of 16 pixels.  The planes are staged in two K chunks of 128
+    // channels; so that every lane has work in both, the lane halves trade registers first: afterwards vs[c] holds
+    // channels 128 c + 4 (lane & 31) .. of the pixels of half (lane >> 5).
+    f32x4 vs[2][8];
+#pragma unroll
+    for (int ps = 0; ps < 8; ++ps) {
+      const u32x4 lo = __builtin_bit_cast(u32x4, vn[0][ps]), hi = __builtin_bit_cast(u32x4, vn[1][ps]);
+      u32x4 slo, shi;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const unsigned a0 = lo[t], a1 = hi[t];
+        const auto sw = __builtin_amdgcn_permlane32_swap(a0, a1, false, false);   // lanes 32.. of a0 <-> lanes 0..31 of a1
+        slo[t] = sw[0];
+        shi[t] = sw[1];
+      }
+      vs[0][ps] = __builtin_bit_cast(f32x4, slo);
+      vs[1][ps] = __builtin_bit_cast(f32x4, shi);
+    }
+    const int kcl = (lane & 31) >> 2, kqn = lane & 3;
+    int an_frag[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      const int m = (a0 + a) * 32 + frow;
+      an_frag[a] = m * 32 + ((fk ^ ((m >> 3) & 1)) << 4);
+    }
+    f32x16 accn[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) accn[a][r] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+#pragma unroll
+      for (int ps = 0; ps < 8; ++ps) {
+        const int i = (lane >> 5) * 32 + er0 + ps * 4;
+        u32x2 hh, mm, ll;
+        split3p(vs[c][ps], hh, mm, ll);
+        unsigned char* d = lds + kcl * KSN + i * 32 + (((kqn >> 1) ^ ((i >> 3) & 1)) << 4) + (kqn & 1) * 8;
+        *reinterpret_cast<u32x2*>(d) = hh;
+        *reinterpret_cast<u32x2*>(d + PLN) = mm;
+        *reinterpret_cast<u32x2*>(d + 2 * PLN) = ll;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k8 = 0; k8 < KCH; ++k8) {
+        const int kc = c * KCH + k8;
+        if (kc + 2 < KCN) load_bn(kc + 2, fn[(kc + 2) % 3]);
+        __builtin_amdgcn_sched_barrier(0);
+        const bf16x8 (&fbn)[NS] = fn[kc % 3];
+        bf16x8 fan[NS][NA];
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+          for (int a = 0; a < NA; ++a) fan[s][a] = *reinterpret_cast<const bf16x8*>(lds + s * PLN + k8 * KSN + an_frag[a]);
+#pragma unroll
+        for (int tt = NS - 1; tt >= 0; --tt)
+#pragma unroll
+          for (int i = 0; i <= tt; ++i)
+#pragma unroll
+            for (int a = 0; a < NA; ++a)
+              accn[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fan[i][a], fbn[tt - i], accn[a], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      __syncthreads();                                              // every wave is done with this chunk's planes
+    }
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = (a0 + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        scratch[i * LDH + tn * 32 + (lane & 31)] = accn[a][r];
+      }
+    __syncthreads();
+    constexpr int TPRN = NEXT / 4, RPPN = kThreads / TPRN, EPN = 64 / RPPN;   // threads per pixel, pixels per pass, passes
+    const int n4 = (tid % TPRN) * 4, nr0 = tid / TPRN;
+    f32x4 biasn = {0.f, 0.f, 0.f, 0.f};
+    if (ga.bias1n) biasn = *reinterpret_cast<const f32x4*>(ga.bias1n + n4);
+    const __amdgpu_buffer_rsrc_t h_rsrc =
+        __builtin_amdgcn_make_buffer_rsrc(ga.h, 0, (int)((size_t)g.N * g.H * g.W * NEXT * 4), 0x00020000);
+#pragma unroll
+    for (int ps = 0; ps < EPN; ++ps) {
+      const int m = nr0 + ps * RPPN;
+      const int ho = ty * 8 + (m >> 3), wo = tx * 8 + (m & 7);
+      f32x4 v = *reinterpret_cast<const f32x4*>(scratch + m * LDH + n4);
+      v += biasn;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) v[t] = fmaxf(v[t], 0.f);
+      if (ho < g.H && wo < g.W)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), h_rsrc, (((n * g.H + ho) * g.W + wo) * NEXT + n4) * 4, 0, 0);
+    }
   }
 }
 
@@ -306,6 +452,50 @@ int bgs_internal_bottleneck_tail_planes(const float* x, const void* w2split, con
   g.tiles_x = (W + 7) / 8;
   g.tiles = N * g.tiles_y * g.tiles_x;
   g.chunk = (g.tiles + 7) / 8;
-  hipLaunchKernelGGL(bottleneck_tail_planes_kernel, dim3((unsigned)(8 * g.chunk)), dim3(kThreads), 0, st, g);
+  hipLaunchKernelGGL(bottleneck_tail_planes_kernel<0>, dim3((unsigned)(8 * g.chunk)), dim3(kThreads), 0, st, g);
+  return hipGetLastError() == hipSuccess ? BGS_OK : BGS_ERR_LAUNCH;
+}
+
+// 1 when bgs_conv3x3_c3_next_fused_nhwc_f32_bfx runs this shape (every map size: whether a map is worth one launch is
+// the caller's decision); pure host logic
+extern "C" int bgs_conv3x3_c3_next_eligible(int N, int H, int W, int Cmid, int Cout3, int Cnext) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cmid != 64 || Cout3 != 256 || (Cnext != 64 && Cnext != 128)) return 0;
+  return (long long)N * H * W * 256 * 4 < (long long)kOob ? 1 : 0;
+}
+
+// bgs_conv3x3_c3_fused_nhwc_f32_bfx with the NEXT block's conv1 in its epilogue: h [N,H,W,Cnext] =
+// relu(conv1x1(y, w1n) + bias1n), w1n_split = bgs_conv_bfx_split_weights of the folded filter [Cnext][Cout3].
+extern "C" int bgs_conv3x3_c3_next_fused_nhwc_f32_bfx(const float* x, const void* w2split, const float* bias2,
+                                                      const void* w3split, const float* bias3, const float* residual,
+                                                      float* y, const void* w1n_split, const float* bias1n, float* h,
+                                                      int N, int H, int W, int Cmid, int Cout3, int relu3, int Cnext,
+                                                      bgs_stream_t stream) {
+  if (N <= 0 || H <= 0 || W <= 0 || !x || !w2split || !w3split || !y || !w1n_split || !h) return BGS_ERR_INVALID_ARG;
+  if (!bgs_conv3x3_c3_next_eligible(N, H, W, Cmid, Cout3, Cnext)) return BGS_ERR_UNSUPPORTED;
+  if (((uintptr_t)x | (uintptr_t)w2split | (uintptr_t)w3split | (uintptr_t)y | (uintptr_t)residual | (uintptr_t)bias2 |
+       (uintptr_t)bias3 | (uintptr_t)w1n_split | (uintptr_t)bias1n | (uintptr_t)h) % 16 != 0)
+    return BGS_ERR_UNSUPPORTED;
+  TailNextArgs a;
+  TailArgs& g = a.t;
+  g.x = x;
+  g.ws2 = reinterpret_cast<const __bf16*>(w2split);
+  g.bias2 = bias2;
+  g.ws3 = reinterpret_cast<const __bf16*>(w3split);
+  g.bias3 = bias3;
+  g.res = residual;
+  g.y = y;
+  g.N = N; g.H = H; g.W = W; g.relu3 = relu3;
+  g.tiles_y = (H + 7) / 8;
+  g.tiles_x = (W + 7) / 8;
+  g.tiles = N * g.tiles_y * g.tiles_x;
+  g.chunk = (g.tiles + 7) / 8;
+  a.ws1n = reinterpret_cast<const __bf16*>(w1n_split);
+  a.bias1n = bias1n;
+  a.h = h;
+  const dim3 grid((unsigned)(8 * g.chunk)), block(kThreads);
+  if (Cnext == 64) hipLaunchKernelGGL(bottleneck_tail_planes_kernel<64>, grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(bottleneck_tail_planes_kernel<128>, grid, block, 0, (hipStream_t)stream, a);
+  bgs_internal_census_bump(BGS_CENSUS_FUSED_C3);
+  bgs_internal_census_bump(BGS_CENSUS_FUSED_C3_NEXT);
   return hipGetLastError() == hipSuccess ? BGS_OK : BGS_ERR_LAUNCH;
 }

@@ -961,7 +961,7 @@ def conv_bfx_last_launch():
 
 CENSUS = dict(bf16_ring8=0, grouped_lds=1, halo_bfx4=2, dma_ring64=3, gs_head_fused=4, conv1x1_bres=5,
               wgrad_bfx=6, roi_bwd_gather=7, bf16s=8, grouped_bf16s=9, bfx_wide=10, gs_scale_grad=11, halo_wide=12, stem_fused=13, fused_c3=14,
-              planes_3x3=15, planes_1x1=16, planes_3x3_head=17)
+              planes_3x3=15, planes_1x1=16, planes_3x3_head=17, fused_c3_next=18)
 
 
 def launch_census(reset=False):
@@ -1058,6 +1058,51 @@ def conv3x3_c3_fused_nhwc(x, w2_krsc, bias2, w3_krsc, bias3, residual=None, relu
                                                Cout3, int(bool(relu3)), capi.current_stream(x.device))
     capi.check('bgs_conv3x3_c3_fused_nhwc_f32_bfx', rc)
     return out
+
+
+def fused_c3_next_eligible(x, w2, w3, stride, residual, w1n, b1n=None, stride1n=1, pad1n=0):
+    """May the tail of a frozen bottleneck ALSO emit the next block's conv1 (:func:`conv3x3_c3_next_fused_nhwc`)?
+    :func:`fused_c3_eligible`, and: that conv1 is 1x1 / stride 1 / no padding with 256 -> 64 or 128 channels, it is frozen
+    and nothing needs a gradient, the arithmetic is ``bf16x6`` on fp32 storage, the tail is the planes form
+    (``BGS_FUSED_C3_PLANES`` not 0).  ``BGS_TAIL_NEXT_C1=0`` (read per call): the launches of before."""
+    if os.environ.get('BGS_TAIL_NEXT_C1', '1') == '0' or os.environ.get('BGS_FUSED_C3_PLANES', '1') == '0':
+        return False
+    if w1n is None or w1n.dim() != 4 or stride1n != 1 or pad1n != 0:
+        return False
+    if tuple(w1n.shape[1:]) != (1, 1, 256) or w1n.shape[0] not in (64, 128) or w1n.dtype != torch.float32:
+        return False
+    if torch.is_grad_enabled() and (w1n.requires_grad or (b1n is not None and b1n.requires_grad)):
+        return False
+    if not fused_c3_eligible(x, w2, w3, stride, residual):
+        return False
+    N, H, W, _ = x.shape
+    return bool(capi.load().bgs_conv3x3_c3_next_eligible(N, H, W, 64, 256, w1n.shape[0]))
+
+
+def conv3x3_c3_next_fused_nhwc(x, w2_krsc, bias2, w3_krsc, bias3, w1n_krsc, bias1n, residual=None, relu3=True):
+    """:func:`conv3x3_c3_fused_nhwc` with the NEXT block's conv1 in the same launch -> ``(y, h)``,
+    ``h = relu(conv1x1(y, w1n) + bias1n)`` ``[N,H,W,Cnext]``; both bit-identical to the two calls it replaces
+    (``conv3x3_c3_fused_nhwc``, then ``conv2d_nhwc(y, w1n, bias1n, relu=True)``).  Forward only, frozen filters."""
+    _require_cuda(x, w2_krsc, bias2, w3_krsc, bias3, w1n_krsc, bias1n, residual)
+    lib = capi.load()
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
+    N, H, W, Cmid = x.shape
+    Cout3, Cnext = w3_krsc.shape[0], w1n_krsc.shape[0]
+    assert tuple(w2_krsc.shape) == (Cmid, 3, 3, Cmid) and tuple(w3_krsc.shape) == (Cout3, 1, 1, Cmid)
+    assert tuple(w1n_krsc.shape) == (Cnext, 1, 1, Cout3) and w1n_krsc.is_contiguous()
+    if residual is not None:
+        assert tuple(residual.shape) == (N, H, W, Cout3) and residual.is_contiguous() and residual.dtype == torch.float32
+    y = torch.empty((N, H, W, Cout3), dtype=torch.float32, device=x.device)
+    h = torch.empty((N, H, W, Cnext), dtype=torch.float32, device=x.device)
+    w2s = bfx_split_weights(w2_krsc.view(Cmid, 9 * Cmid), cache=True)
+    w3s = bfx_split_weights(w3_krsc.view(Cout3, Cmid), cache=True)
+    w1s = bfx_split_weights(w1n_krsc.view(Cnext, Cout3), cache=True)
+    rc = lib.bgs_conv3x3_c3_next_fused_nhwc_f32_bfx(capi.ptr(x), capi.ptr(w2s), capi.ptr(bias2), capi.ptr(w3s),
+                                                    capi.ptr(bias3), capi.ptr(residual), capi.ptr(y), capi.ptr(w1s),
+                                                    capi.ptr(bias1n), capi.ptr(h), N, H, W, Cmid, Cout3,
+                                                    int(bool(relu3)), Cnext, capi.current_stream(x.device))
+    capi.check('bgs_conv3x3_c3_next_fused_nhwc_f32_bfx', rc)
+    return y, h
 
 
 def rpn_head_fusion_eligible(x, w_conv, w_head):

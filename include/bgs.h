@@ -374,6 +374,19 @@ int bgs_conv3x3_c3_fused_nhwc_f32_bfx(const float* x, const void* w2split, const
                                       const void* w3split, const float* bias3, const float* residual,
                                       float* y, int N, int H, int W, int Cmid, int Cout3, int relu3,
                                       bgs_stream_t stream);
+/* ... with the NEXT block's conv1 (1x1 / stride 1, Cout3 -> Cnext, folded BN bias1n, ReLU; resnet.py:220-232) in the
+ * epilogue of the same launch: a workgroup of bottleneck_tail_planes_kernel holds all Cout3 channels of its 8 x 8 pixels
+ * and a 1x1 conv needs no halo.  w1n_split = bgs_conv_bfx_split_weights of the folded filter [Cnext][Cout3];
+ * h [N,H,W,Cnext] = relu(conv1x1(y, w1n) + bias1n).  y is stored as before (it is the next block's residual); what goes
+ * away is the launch that reads it back.  Forward only, frozen filters.  Supported: Cmid = 64, Cout3 = 256, Cnext = 64 |
+ * 128, every map size (bgs_conv3x3_c3_next_eligible: host logic only); BGS_ERR_UNSUPPORTED otherwise.  Both outputs
+ * BIT-IDENTICAL to bgs_conv3x3_c3_fused_nhwc_f32_bfx followed by bgs_conv2d_nhwc_f32_bfx_ws with one K slice. */
+int bgs_conv3x3_c3_next_fused_nhwc_f32_bfx(const float* x, const void* w2split, const float* bias2,
+                                           const void* w3split, const float* bias3, const float* residual,
+                                           float* y, const void* w1n_split, const float* bias1n, float* h,
+                                           int N, int H, int W, int Cmid, int Cout3, int relu3, int Cnext,
+                                           bgs_stream_t stream);
+int bgs_conv3x3_c3_next_eligible(int N, int H, int W, int Cmid, int Cout3, int Cnext);
 /* The RPN head of a level in ONE launch (mmdet/models/anchor_heads/rpn_head.py:30-35): rpn_conv (3x3 / stride 1 /
  * pad 1, Cin -> 256, bias, ReLU when relu != 0) with rpn_cls + rpn_reg (one 1x1 filter [Chead][256], Chead <= 32) in its
  * epilogue — the HEAD form of the 8 x 8-pixel planes kernel (csrc/conv3x3_planes.hip), whose workgroups own all 256

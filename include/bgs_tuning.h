@@ -51,6 +51,7 @@ int bgs_selftest_mfma_peak_bf16(int blocks, int iters, int random_operands, floa
 #define BGS_CENSUS_PLANES_3X3 15      /* conv3x3_planes_bfx_kernel (8 x 8 pixels, whole reduction per workgroup) */
 #define BGS_CENSUS_PLANES_1X1 16      /* conv1x1_planes_bfx_kernel (A split once per K chunk into LDS planes)    */
 #define BGS_CENSUS_PLANES_3X3_HEAD 17 /* conv3x3_planes_bfx_kernel<2, true> (rpn_conv + the 1x1 RPN heads; also counted in 15) */
+#define BGS_CENSUS_FUSED_C3_NEXT 18  /* bottleneck_tail_planes_kernel<64 | 128> (the tail + the next block's conv1; also counted in 14) */
 #define BGS_CENSUS_FAMILIES 20
 int bgs_launch_census(int family, int reset);
 
