@@ -260,7 +260,17 @@ class Bottleneck(nn.Module):
         xin = x
         identity = x
         fk = None
-        if 'ds' in f and not fuse and x.is_cuda and BF.shortcut_fork_enabled() and \
+        # frozen layer1.0 (1x1 / stride-1 shortcut, 64 -> 256, in front of the fused tail): the tail launch computes the
+        # shortcut itself from x (csrc/bottleneck_tail_planes.hip, SC form; bit-identical) — no shortcut launch, no fork.
+        # Decided here, before the fork: conv1 is 1x1 / stride 1, so the tail's input shape is known from x.
+        sc_tail = ('ds' in f and not fuse and self.groups == 1 and not self.with_dcn and x.is_cuda and
+                   not (torch.is_grad_enabled() and any(t.requires_grad for k in ('c1', 'c2', 'c3', 'ds') for t in f[k]
+                                                        if t is not None)) and
+                   BF.fused_c3_shortcut_eligible(x, tuple(x.shape[:3]) + (f['c1'][0].shape[0],), f['c2'][0], f['c3'][0],
+                                                 self.stride, f['ds'][0], f['ds'][1], self.stride))
+        if sc_tail:
+            identity = None
+        elif 'ds' in f and not fuse and x.is_cuda and BF.shortcut_fork_enabled() and \
                 not (torch.is_grad_enabled() and any(t.requires_grad for t in f['ds'] if t is not None)):
             # frozen block: the projection shortcut (a 1x1 / stride-s conv of the block input) is independent of
             # conv1 -> conv2 and runs beside them on the side stream; conv3's epilogue consumes it after the join
@@ -300,6 +310,13 @@ class Bottleneck(nn.Module):
                                      passthrough=first_pt)
             if first_pt:
                 out, identity = out
+        if sc_tail:
+            if BF.fused_c3_eligible(out, f['c2'][0], f['c3'][0], self.stride, None):
+                nc = next_c1 if next_c1 is not None and next_c1[0].shape[0] == 64 and BF.fused_c3_next_eligible(
+                    out, f['c2'][0], f['c3'][0], self.stride, None, next_c1[0], next_c1[1]) else (None, None)
+                return BF.conv3x3_c3_sc_fused_nhwc(out, f['c2'][0], f['c2'][1], f['c3'][0], f['c3'][1], x, f['ds'][0],
+                                                   f['ds'][1], nc[0], nc[1], relu3=True)
+            identity = BF.conv2d_nhwc(x, f['ds'][0], f['ds'][1], stride=self.stride)   # (the tail declined conv1's output)
         if not fuse and BF.fused_c3_eligible(out, f['c2'][0], f['c3'][0], self.stride, identity):
             # frozen 64 -> 64 -> 256 block on a large map (ResNet-50 layer1): conv2 -> conv3 + residual + ReLU in one
             # launch, the 64-channel intermediate stays in LDS (csrc/conv_bfx.hip, round 6; bit-identical)

@@ -109,6 +109,10 @@ SIGNATURES = {
                                                [c_f32p, c_ptr, c_f32p, c_ptr, c_f32p, c_f32p, c_f32p, c_ptr, c_f32p,
                                                 c_f32p] + [ctypes.c_int] * 7 + [c_ptr]),
     'bgs_conv3x3_c3_next_eligible': (ctypes.c_int, [ctypes.c_int] * 6),
+    'bgs_conv3x3_c3_sc_fused_nhwc_f32_bfx': (ctypes.c_int,
+                                             [c_f32p, c_ptr, c_f32p, c_ptr, c_f32p, c_f32p, c_ptr, c_f32p, c_f32p, c_ptr,
+                                              c_f32p, c_f32p] + [ctypes.c_int] * 8 + [c_ptr]),
+    'bgs_conv3x3_c3_sc_eligible': (ctypes.c_int, [ctypes.c_int] * 7),
     'bgs_conv3x3_halo_nhwc_f32_bfx': (ctypes.c_int, [c_f32p, c_ptr, c_f32p, c_f32p]
                                       + [ctypes.c_int] * 7 + [c_ptr, ctypes.c_size_t, c_ptr]),
     'bgs_conv3x3_halo_nhwc_f32_bfx_ex': (ctypes.c_int, [c_f32p, c_ptr, c_f32p, c_f32p, c_f32p]

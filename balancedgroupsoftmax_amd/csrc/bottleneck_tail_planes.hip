@@ -29,6 +29,24 @@
 //     to the launch it replaces.  No accumulator changes hands and no K range is split;
 //   * bias, ReLU and 16-byte stores of h [N,H,W,NEXT] through the LDS transpose.
 // LDS 48.75 KB, <= 156 VGPRs: still three workgroups per CU.  NEXT = 0 is the kernel above, instruction for instruction.
+//
+// SC (NEXT = 0 | 64): the block's own PROJECTION SHORTCUT (1x1 / stride 1, 64 -> 256, folded BN: layer1.0's downsample)
+// in the epilogue, in place of the residual map another launch wrote only to be read back here.  conv3 is a conv of this
+// very shape, so the shortcut is phase 3's loop over another A operand and another filter:
+//   * the block input x0 of the tile's 64 pixels (16 KB: four 16-byte loads per thread) waits in registers: the quads of
+//     epilogue half 0 are loaded with the patch of phase 0, those of half 1 under conv3's last k step into the registers
+//     its first filter set leaves (all four from phase 0 on spilled: phase 3 is the register peak); outside the image x0
+//     reads 0 through the descriptor;
+//   * per 32-pixel half of the epilogue the half's x0 is split (the same split3) into A planes BEHIND the epilogue's
+//     half tile ([plane][k step][pixel][32 B], phase 3's layout, k steps 32 B further apart than their 1 KB); wave w
+//     reduces its two 32 x 32 tiles (channels 64 w ..) one after the other, each in an accumulator of its OWN that starts
+//     at zero (never in acc3), four k steps ascending, the six plane products in phase 3's order, filter fragments from
+//     L2 one step ahead — the summation order of the stand-alone 1x1 kernels;
+//   * (acc3 + bias3) + (acc_sc + bias_sc) is formed in the MFMA register layout (a lane owns one channel per 32-wide
+//     tile), in the order the two launches add — fp32(acc_sc + bias_sc) is what the stand-alone shortcut stores — so
+//     the transposed value only needs the clamp: y (and h) BIT-IDENTICAL to the shortcut launch followed by the tail;
+//   * half 1's planes are written while half 0's tile is stored: four barriers in the epilogue, as without SC.
+// LDS 46,464 B (NEXT = 64: 49,920), no scratch memory: three workgroups per CU.  The SC = false kernels are unchanged.
 #include <stdlib.h>
 
 #include "conv_args.h"
@@ -77,17 +95,57 @@ struct TailNextArgs {
   const float* bias1n;   // [NEXT] or null
   float* h;              // [N,H,W,NEXT]
 };
-template <int NEXT> struct TailArgsOf { typedef TailNextArgs type; };
-template <> struct TailArgsOf<0> { typedef TailArgs type; };
+template <class A> struct TailScArgs {
+  A a;                   // (a.t.res / a.res: unused)
+  const float* x0;       // block input [N,H,W,64]
+  const __bf16* wssc;    // split shortcut filter [3][4][256][16]
+  const float* bias_sc;  // [256] or null
+};
+template <int NEXT, bool SC = false> struct TailArgsOf { typedef TailNextArgs type; };
+template <> struct TailArgsOf<0, false> { typedef TailArgs type; };
+template <int NEXT> struct TailArgsOf<NEXT, true> { typedef TailScArgs<typename TailArgsOf<NEXT>::type> type; };
 __device__ __forceinline__ const TailArgs& tail_base(const TailArgs& a) { return a; }
 __device__ __forceinline__ const TailArgs& tail_base(const TailNextArgs& a) { return a.t; }
+template <class A> __device__ __forceinline__ const TailArgs& tail_base(const TailScArgs<A>& a) { return tail_base(a.a); }
+template <class A> __device__ __forceinline__ const A& tail_inner(const A& a) { return a; }
+template <class A> __device__ __forceinline__ const A& tail_inner(const TailScArgs<A>& a) { return a.a; }
 
 constexpr int kOob = 0x7f000000;   // byte offset past every descriptor this kernel builds: the load returns 0
 
-template <int NEXT>
-__global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typename TailArgsOf<NEXT>::type ga) {
+// (SC) this thread's two quads of the block input x0 [N,H,W,64] for 32-pixel half `a` of tile (n, ty, tx): 16 threads per
+// pixel, pixels 32 a + (tid >> 4) and 16 further, channels 4 (tid & 15) ..; outside the image: 0
+__device__ __forceinline__ void load_x0_half(const float* x0, const TailArgs& g, int n, int ty, int tx, int tid, int a,
+                                             f32x4& q0, f32x4& q1) {
+  const __amdgpu_buffer_rsrc_t x0_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<float*>(x0), 0, (int)((size_t)g.N * g.H * g.W * 64 * 4), 0x00020000);
+  f32x4 q[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int m = a * 32 + (tid >> 4) + 16 * j;
+    const int ho = ty * 8 + (m >> 3), wo = tx * 8 + (m & 7);
+    const int off = ho < g.H && wo < g.W ? (((n * g.H + ho) * g.W + wo) * 64 + (tid & 15) * 4) * 4 : kOob;
+    q[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x0_rsrc, off, 0, 0));
+  }
+  q0 = q[0];
+  q1 = q[1];
+}
+
+// (SC) shortcut filter fragments of step t = 4 b + kc: k step kc of the wave's tile b (rows wave * 64 + 32 b .. of the split
+// filter [3][4][256][16]; lane_off: the wave's conv3 fragment offset).  One tile at a time keeps the shortcut's accumulator
+// and its two fragment sets at 40 registers.
+__device__ __forceinline__ void load_sc_filter(const __bf16* wssc, int lane_off, int t, bf16x8 (&dst)[3]) {
+  const __amdgpu_buffer_rsrc_t bs_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(wssc), 0, 3 * 4 * 256 * 32, 0x00020000);
+#pragma unroll
+  for (int s = 0; s < 3; ++s)
+    dst[s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(bs_rsrc, lane_off, ((s * 4 + (t & 3)) * 256 + 32 * (t >> 2)) * 32, 0));
+}
+
+template <int NEXT, bool SC = false>
+__global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typename TailArgsOf<NEXT, SC>::type ga) {
   static_assert(NEXT == 0 || NEXT == 64 || NEXT == 128, "width of the next block's conv1");
+  static_assert(!SC || NEXT != 128, "a block with a stride-1 projection shortcut (layer1.0) is never in front of a 128-wide conv1");
   const TailArgs& g = tail_base(ga);
+  const auto& gn = tail_inner(ga);
   constexpr int NS = 3, CM = 64, CO3 = 256, KC2 = 36, KC3 = 4;
   constexpr int PW = 10, PS = 12, PSLOTS = PW * PS;                 // 10 x 10 patch in rows of 12 slots
   constexpr int AQ = PW * PW * 16, AQT = (AQ + kThreads - 1) / kThreads;   // 1600 fp32 quads: 7 per thread (the 7th: 64 threads)
@@ -95,13 +153,17 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
   // conv1' A planes (NEXT > 0), one 128-deep K chunk of the 64 pixels at a time: 8 k steps of 2 KB + 32 B (the lanes
   // that hold one pixel write 8 k steps at once), 16,640 per plane, 49,920 in all
   constexpr int KCN = CO3 / 16, KCH = KCN / 2, KSN = 64 * 32 + 32, PLN = KCH * KSN;
-  constexpr int LDS_BYTES = NEXT ? NS * PLN : NS * PL;              // 46,080 (NEXT > 0: 49,920)
+  constexpr int LD4 = CO3 + 8;                                      // epilogue half tile: 32 x 264 x 4 = 33,792 (overlays both)
+  // shortcut A planes (SC) of one 32-pixel half behind the epilogue's half tile: 4 k steps of 1 KB + 32 B, 4,224 per
+  // plane, 33,792 .. 46,464
+  constexpr int SC_OFF = 32 * LD4 * 4, KSC = 32 * 32 + 32, PLSC = KC3 * KSC;
+  constexpr int LDS_BASE = NEXT ? NS * PLN : NS * PL;               // 46,080 (NEXT > 0: 49,920)
+  constexpr int LDS_BYTES = SC && SC_OFF + NS * PLSC > LDS_BASE ? SC_OFF + NS * PLSC : LDS_BASE;   // (SC, NEXT = 0: 46,464)
   static_assert(64 * (NEXT + 8) * 4 <= LDS_BYTES, "the h transpose tile overlays the planes");
   static_assert(NS * PL <= LDS_BYTES && 3 * LDS_BYTES <= 160 * 1024, "three workgroups per CU");
   constexpr int LD2 = CM + 4, S2_BYTES = 64 * LD2 * 4;              // conv2 transpose tile: 17,408 at offset 0
   constexpr int Y_OFF = 18 * 1024;                                  // conv3's A planes behind it: 18,432 .. 43,008
   constexpr int P3_CH = 64 * 32, P3_PL = KC3 * P3_CH;               // 2 KB per k step, 8 KB per plane
-  constexpr int LD4 = CO3 + 8;                                      // epilogue half tile: 32 x 264 x 4 = 33,792 (overlays both)
   static_assert(S2_BYTES <= Y_OFF && Y_OFF + NS * P3_PL <= LDS_BYTES && 32 * LD4 * 4 <= LDS_BYTES, "overlays");
   __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS_BYTES];
 
@@ -134,6 +196,12 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
     const int quad = kq & 3;
     a_dst[i] = use ? (kq >> 2) * KS + (ppy * PS + ppx) * 32 + (((quad >> 1) ^ (ppy & 1)) << 4) + (quad & 1) * 8 : -1;
   }
+
+  // (SC) the block input of the tile's own 64 pixels, 16 threads per pixel: rx[2 a + j] = pixel 32 a + 16 j + (tid >> 4),
+  // channels 4 (tid & 15) ...  Half 0's quads arrive with the patch and wait in registers for the epilogue; half 1's are
+  // loaded under conv3's last k step, into the registers its first filter set leaves (phase 3 is the register peak)
+  f32x4 rx[SC ? 4 : 1];
+  if constexpr (SC) load_x0_half(ga.x0, g, n, ty, tx, tid, 0, rx[0], rx[1]);
 
   // conv2 filter fragments: wave (wm, wn) reads rows 32 wn .. of the 64
   const __amdgpu_buffer_rsrc_t b2_rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -203,6 +271,7 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
   };
   bf16x8 f3a[NS][2], f3b[NS][2];
   load_b3(0, f3a);
+  bf16x8 fsa[NS], fsb[NS];                                          // (SC) the shortcut's filter fragments
 
   // ---- phase 2: conv2 tile -> fp32 transpose -> bias2, ReLU, split -> conv3's A planes
   __syncthreads();                                                  // every wave is done with the patch planes
@@ -255,6 +324,12 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
       if (kc & 1) load_b3(kc + 1, f3a);
       else load_b3(kc + 1, f3b);
     }
+    if constexpr (SC) {
+      if (kc == KC3 - 1) {                                          // f3a is free: the shortcut's first filter set, then half 1 of x0
+        load_sc_filter(ga.wssc, b3_lane, 0, fsa);
+        load_x0_half(ga.x0, g, n, ty, tx, tid, 1, rx[2], rx[3]);
+      }
+    }
     __builtin_amdgcn_sched_barrier(0);
     const bf16x8 (&fb3)[NS][2] = (kc & 1) ? f3b : f3a;
     bf16x8 fa3[NS][2];
@@ -284,6 +359,87 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
       const_cast<float*>(g.res ? g.res : g.x), 0, g.res ? out_bytes : 0, 0x00020000);     // 0 bytes: every read is 0
   const __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(g.y, 0, out_bytes, 0x00020000);
   f32x4 vn[NEXT ? 2 : 1][NEXT ? 8 : 1];                             // (NEXT > 0) this thread's final values, both halves
+  if constexpr (SC) {
+    // the shortcut by halves: planes of the half -> 48 MFMAs per wave -> (acc3 + bias3) + (acc_sc + bias_sc) in the MFMA
+    // layout -> transpose -> clamp, store.  The planes lie behind the half tile, so half 1's are written under half 0's
+    // stores and the epilogue keeps its four barriers.
+    const int kcw = (tid & 15) >> 2, kqw = tid & 3;
+    auto write_planes = [&](int a) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int i = (tid >> 4) + 16 * j;
+        u32x2 hh, mm, ll;
+        split3p(rx[2 * a + j], hh, mm, ll);
+        unsigned char* d = lds + SC_OFF + kcw * KSC + i * 32 + (((kqw >> 1) ^ ((i >> 3) & 1)) << 4) + (kqw & 1) * 8;
+        *reinterpret_cast<u32x2*>(d) = hh;
+        *reinterpret_cast<u32x2*>(d + PLSC) = mm;
+        *reinterpret_cast<u32x2*>(d + 2 * PLSC) = ll;
+      }
+    };
+    const int as_frag = SC_OFF + frow * 32 + ((fk ^ ((frow >> 3) & 1)) << 4);
+    // a lane of the MFMA layout owns channel wave * 64 + 32 b + (lane & 31) of its two tiles
+    float b3v[2] = {0.f, 0.f}, bsv[2] = {0.f, 0.f};
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      if (g.bias3) b3v[b] = g.bias3[wave * 64 + b * 32 + (lane & 31)];
+      if (ga.bias_sc) bsv[b] = ga.bias_sc[wave * 64 + b * 32 + (lane & 31)];
+    }
+    write_planes(0);
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      __syncthreads();                                              // the half's planes are there (a = 1: and half 0's tile is read)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        f32x16 accs;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) accs[r] = 0.f;
+#pragma unroll
+        for (int kc = 0; kc < KC3; ++kc) {
+          const int t = b * KC3 + kc;
+          if (t + 1 < 2 * KC3) {
+            if (t & 1) load_sc_filter(ga.wssc, b3_lane, t + 1, fsa);
+            else load_sc_filter(ga.wssc, b3_lane, t + 1, fsb);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          const bf16x8 (&fbs)[NS] = (t & 1) ? fsb : fsa;
+          bf16x8 fas[NS];
+#pragma unroll
+          for (int s = 0; s < NS; ++s) fas[s] = *reinterpret_cast<const bf16x8*>(lds + as_frag + kc * KSC + s * PLSC);
+#pragma unroll
+          for (int tt = NS - 1; tt >= 0; --tt)
+#pragma unroll
+            for (int i = 0; i <= tt; ++i) accs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fas[i], fbs[tt - i], accs, 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int i = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+          const float rsc = accs[r] + bsv[b];                       // what the stand-alone shortcut stores
+          scratch[i * LD4 + wave * 64 + b * 32 + (lane & 31)] = (acc3[a][b][r] + b3v[b]) + rsc;
+        }
+      }
+      __syncthreads();
+      if (a == 0) {                                                 // every wave is done with half 0's planes
+        load_sc_filter(ga.wssc, b3_lane, 0, fsa);
+        write_planes(1);
+      }
+#pragma unroll
+      for (int ps = 0; ps < 8; ++ps) {
+        const int i = er0 + ps * 4;
+        const int m = a * 32 + i;
+        const int ho = ty * 8 + (m >> 3), wo = tx * 8 + (m & 7);
+        f32x4 v = *reinterpret_cast<const f32x4*>(scratch + i * LD4 + e4);
+        if (g.relu3) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) v[t] = fmaxf(v[t], 0.f);
+        }
+        if (ho < g.H && wo < g.W)
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), y_rsrc, (((n * g.H + ho) * g.W + wo) * CO3 + e4) * 4, 0, 0);
+        if constexpr (NEXT > 0) vn[a][ps] = v;
+      }
+    }
+    if constexpr (NEXT > 0) __syncthreads();                        // half 1's tile is read: phase 5 overlays it
+  } else {
 #pragma unroll
   for (int a = 0; a < 2; ++a) {
     f32x4 rs[8];
@@ -319,6 +475,7 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
     }
     __syncthreads();
   }
+  }
 
   if constexpr (NEXT > 0) {
     // ---- phase 5: the next block's conv1 on the 64 pixels x 256 channels this workgroup has just stored.  Every 32 x 32
@@ -328,7 +485,7 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
     const int a0 = NEXT == 128 ? 0 : (wave >> 1);
     const int tn = NEXT == 128 ? wave : (wave & 1);
     const __amdgpu_buffer_rsrc_t bn_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<__bf16*>(ga.ws1n), 0, NS * KCN * NEXT * 32, 0x00020000);
+        const_cast<__bf16*>(gn.ws1n), 0, NS * KCN * NEXT * 32, 0x00020000);
     const int bn_lane = ((tn * 32 + frow) * 16 + fk * 8) * 2;       // bytes
     auto load_bn = [&](int kc, bf16x8 (&dst)[NS]) {
 #pragma unroll
@@ -414,9 +571,9 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
     constexpr int TPRN = NEXT / 4, RPPN = kThreads / TPRN, EPN = 64 / RPPN;   // threads per pixel, pixels per pass, passes
     const int n4 = (tid % TPRN) * 4, nr0 = tid / TPRN;
     f32x4 biasn = {0.f, 0.f, 0.f, 0.f};
-    if (ga.bias1n) biasn = *reinterpret_cast<const f32x4*>(ga.bias1n + n4);
+    if (gn.bias1n) biasn = *reinterpret_cast<const f32x4*>(gn.bias1n + n4);
     const __amdgpu_buffer_rsrc_t h_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(ga.h, 0, (int)((size_t)g.N * g.H * g.W * NEXT * 4), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(gn.h, 0, (int)((size_t)g.N * g.H * g.W * NEXT * 4), 0x00020000);
 #pragma unroll
     for (int ps = 0; ps < EPN; ++ps) {
       const int m = nr0 + ps * RPPN;
@@ -497,5 +654,68 @@ extern "C" int bgs_conv3x3_c3_next_fused_nhwc_f32_bfx(const float* x, const void
   else hipLaunchKernelGGL(bottleneck_tail_planes_kernel<128>, grid, block, 0, (hipStream_t)stream, a);
   bgs_internal_census_bump(BGS_CENSUS_FUSED_C3);
   bgs_internal_census_bump(BGS_CENSUS_FUSED_C3_NEXT);
+  return hipGetLastError() == hipSuccess ? BGS_OK : BGS_ERR_LAUNCH;
+}
+
+// 1 when bgs_conv3x3_c3_sc_fused_nhwc_f32_bfx runs this shape: the tail of a 64 -> 64 -> 256 bottleneck whose 1x1 /
+// stride-1 projection shortcut reads Cin0 = 64 channels, with or without a 64-wide next conv1; pure host logic
+extern "C" int bgs_conv3x3_c3_sc_eligible(int N, int H, int W, int Cin0, int Cmid, int Cout3, int Cnext) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cin0 != 64 || Cmid != 64 || Cout3 != 256 || (Cnext != 0 && Cnext != 64)) return 0;
+  const long long lim = kOob / (256 * 4);                           // pixels; every partial product below stays under 2^62
+  const long long nh = (long long)N * H;
+  if (nh >= lim) return 0;
+  return nh * W < lim ? 1 : 0;
+}
+
+// bgs_conv3x3_c3_fused_nhwc_f32_bfx / bgs_conv3x3_c3_next_fused_nhwc_f32_bfx with the residual COMPUTED in the launch:
+// residual = conv1x1(x0, wsc) + bias_sc, the block's projection shortcut on the block input x0 [N,H,W,Cin0].
+// Cnext = 0: w1n_split, bias1n and h are not used (pass NULL).
+extern "C" int bgs_conv3x3_c3_sc_fused_nhwc_f32_bfx(const float* x, const void* w2split, const float* bias2,
+                                                    const void* w3split, const float* bias3, const float* x0,
+                                                    const void* wsc_split, const float* bias_sc, float* y,
+                                                    const void* w1n_split, const float* bias1n, float* h, int N, int H,
+                                                    int W, int Cin0, int Cmid, int Cout3, int relu3, int Cnext,
+                                                    bgs_stream_t stream) {
+  if (N <= 0 || H <= 0 || W <= 0 || !x || !w2split || !w3split || !x0 || !wsc_split || !y) return BGS_ERR_INVALID_ARG;
+  if (Cnext != 0 && (!w1n_split || !h)) return BGS_ERR_INVALID_ARG;
+  if (!bgs_conv3x3_c3_sc_eligible(N, H, W, Cin0, Cmid, Cout3, Cnext)) return BGS_ERR_UNSUPPORTED;
+  if (((uintptr_t)x | (uintptr_t)w2split | (uintptr_t)w3split | (uintptr_t)y | (uintptr_t)x0 | (uintptr_t)wsc_split |
+       (uintptr_t)bias2 | (uintptr_t)bias3 | (uintptr_t)bias_sc) % 16 != 0)
+    return BGS_ERR_UNSUPPORTED;
+  if (Cnext != 0 && ((uintptr_t)w1n_split | (uintptr_t)bias1n | (uintptr_t)h) % 16 != 0) return BGS_ERR_UNSUPPORTED;
+  TailScArgs<TailNextArgs> a;
+  TailArgs& g = a.a.t;
+  g.x = x;
+  g.ws2 = reinterpret_cast<const __bf16*>(w2split);
+  g.bias2 = bias2;
+  g.ws3 = reinterpret_cast<const __bf16*>(w3split);
+  g.bias3 = bias3;
+  g.res = nullptr;
+  g.y = y;
+  g.N = N; g.H = H; g.W = W; g.relu3 = relu3;
+  g.tiles_y = (H + 7) / 8;
+  g.tiles_x = (W + 7) / 8;
+  g.tiles = N * g.tiles_y * g.tiles_x;
+  g.chunk = (g.tiles + 7) / 8;
+  a.a.ws1n = reinterpret_cast<const __bf16*>(w1n_split);
+  a.a.bias1n = bias1n;
+  a.a.h = h;
+  a.x0 = x0;
+  a.wssc = reinterpret_cast<const __bf16*>(wsc_split);
+  a.bias_sc = bias_sc;
+  const dim3 grid((unsigned)(8 * g.chunk)), block(kThreads);
+  if (Cnext == 64) {
+    hipLaunchKernelGGL((bottleneck_tail_planes_kernel<64, true>), grid, block, 0, (hipStream_t)stream, a);
+    bgs_internal_census_bump(BGS_CENSUS_FUSED_C3_NEXT);
+  } else {
+    TailScArgs<TailArgs> a0;
+    a0.a = g;
+    a0.x0 = a.x0;
+    a0.wssc = a.wssc;
+    a0.bias_sc = a.bias_sc;
+    hipLaunchKernelGGL((bottleneck_tail_planes_kernel<0, true>), grid, block, 0, (hipStream_t)stream, a0);
+  }
+  bgs_internal_census_bump(BGS_CENSUS_FUSED_C3);
+  bgs_internal_census_bump(BGS_CENSUS_FUSED_C3_SHORTCUT);
   return hipGetLastError() == hipSuccess ? BGS_OK : BGS_ERR_LAUNCH;
 }

@@ -961,7 +961,7 @@ def conv_bfx_last_launch():
 
 CENSUS = dict(bf16_ring8=0, grouped_lds=1, halo_bfx4=2, dma_ring64=3, gs_head_fused=4, conv1x1_bres=5,
               wgrad_bfx=6, roi_bwd_gather=7, bf16s=8, grouped_bf16s=9, bfx_wide=10, gs_scale_grad=11, halo_wide=12, stem_fused=13, fused_c3=14,
-              planes_3x3=15, planes_1x1=16, planes_3x3_head=17, fused_c3_next=18)
+              planes_3x3=15, planes_1x1=16, planes_3x3_head=17, fused_c3_next=18, fused_c3_shortcut=19)
 
 
 def launch_census(reset=False):
@@ -1103,6 +1103,65 @@ def conv3x3_c3_next_fused_nhwc(x, w2_krsc, bias2, w3_krsc, bias3, w1n_krsc, bias
                                                     int(bool(relu3)), Cnext, capi.current_stream(x.device))
     capi.check('bgs_conv3x3_c3_next_fused_nhwc_f32_bfx', rc)
     return y, h
+
+
+def fused_c3_shortcut_eligible(x0, h1_shape, w2, w3, stride, w_sc, b_sc=None, stride_sc=1):
+    """May the tail of a frozen bottleneck compute the block's own projection shortcut (:func:`conv3x3_c3_sc_fused_nhwc`)
+    in place of reading the map a shortcut launch wrote?  ``x0``: the block input, ``h1_shape``: the shape of conv1's
+    output (the tail's input; conv1 is 1x1 / stride 1, so it is known from ``x0``).  :func:`fused_c3_eligible` on that
+    shape, and: the shortcut is 1x1 / stride 1 with 64 -> 256 channels, it is frozen and nothing needs a gradient, the
+    arithmetic is ``bf16x6`` on fp32 storage, the tail is the planes form (``BGS_FUSED_C3_PLANES`` not 0).
+    ``BGS_TAIL_SHORTCUT=0`` (read per call): the launches of before."""
+    if os.environ.get('BGS_TAIL_SHORTCUT', '1') == '0' or os.environ.get('BGS_FUSED_C3_PLANES', '1') == '0':
+        return False
+    if w_sc is None or w_sc.dim() != 4 or stride_sc != 1 or stride != 1:
+        return False
+    if tuple(w_sc.shape) != (256, 1, 1, 64) or w_sc.dtype != torch.float32 or not w_sc.is_contiguous():
+        return False
+    if x0.dim() != 4 or x0.shape[3] != 64 or x0.dtype != torch.float32 or not x0.is_cuda or not x0.is_contiguous():
+        return False
+    if tuple(h1_shape) != (x0.shape[0], x0.shape[1], x0.shape[2], 64):
+        return False
+    if torch.is_grad_enabled() and (x0.requires_grad or w_sc.requires_grad or (b_sc is not None and b_sc.requires_grad)):
+        return False
+    # (the tail's own rule; x0 stands in for conv1's output: same device, dtype and shape, and neither needs a gradient)
+    if not fused_c3_eligible(x0, w2, w3, stride, None):
+        return False
+    N, H, W, _ = x0.shape
+    return bool(capi.load().bgs_conv3x3_c3_sc_eligible(N, H, W, 64, 64, 256, 0))
+
+
+def conv3x3_c3_sc_fused_nhwc(x, w2_krsc, bias2, w3_krsc, bias3, x0, w_sc_krsc, bias_sc, w1n_krsc=None, bias1n=None,
+                             relu3=True):
+    """:func:`conv3x3_c3_fused_nhwc` with ``residual = conv1x1(x0, w_sc) + bias_sc`` — the block's 1x1 / stride-1
+    projection shortcut on the block input ``x0`` ``[N,H,W,64]`` — computed inside the launch -> ``y``; with ``w1n_krsc``
+    (the next block's conv1, 256 -> 64) -> ``(y, h)`` as :func:`conv3x3_c3_next_fused_nhwc`.  Bit-identical to
+    ``conv2d_nhwc(x0, w_sc, bias_sc)`` followed by those calls.  Forward only, frozen filters."""
+    _require_cuda(x, w2_krsc, bias2, w3_krsc, bias3, x0, w_sc_krsc, bias_sc, w1n_krsc, bias1n)
+    lib = capi.load()
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
+    N, H, W, Cmid = x.shape
+    Cout3, Cin0 = w3_krsc.shape[0], x0.shape[3]
+    Cnext = 0 if w1n_krsc is None else w1n_krsc.shape[0]
+    assert tuple(w2_krsc.shape) == (Cmid, 3, 3, Cmid) and tuple(w3_krsc.shape) == (Cout3, 1, 1, Cmid)
+    assert tuple(x0.shape) == (N, H, W, Cin0) and x0.is_contiguous() and x0.dtype == torch.float32
+    assert tuple(w_sc_krsc.shape) == (Cout3, 1, 1, Cin0) and w_sc_krsc.is_contiguous()
+    y = torch.empty((N, H, W, Cout3), dtype=torch.float32, device=x.device)
+    w2s = bfx_split_weights(w2_krsc.view(Cmid, 9 * Cmid), cache=True)
+    w3s = bfx_split_weights(w3_krsc.view(Cout3, Cmid), cache=True)
+    wss = bfx_split_weights(w_sc_krsc.view(Cout3, Cin0), cache=True)
+    h = w1s = None
+    if Cnext:
+        assert tuple(w1n_krsc.shape) == (Cnext, 1, 1, Cout3) and w1n_krsc.is_contiguous()
+        h = torch.empty((N, H, W, Cnext), dtype=torch.float32, device=x.device)
+        w1s = bfx_split_weights(w1n_krsc.view(Cnext, Cout3), cache=True)
+    rc = lib.bgs_conv3x3_c3_sc_fused_nhwc_f32_bfx(capi.ptr(x), capi.ptr(w2s), capi.ptr(bias2), capi.ptr(w3s),
+                                                  capi.ptr(bias3), capi.ptr(x0), capi.ptr(wss), capi.ptr(bias_sc),
+                                                  capi.ptr(y), capi.ptr(w1s), capi.ptr(bias1n if Cnext else None),
+                                                  capi.ptr(h), N, H, W, Cin0, Cmid, Cout3, int(bool(relu3)), Cnext,
+                                                  capi.current_stream(x.device))
+    capi.check('bgs_conv3x3_c3_sc_fused_nhwc_f32_bfx', rc)
+    return (y, h) if Cnext else y
 
 
 def rpn_head_fusion_eligible(x, w_conv, w_head):

@@ -387,6 +387,21 @@ int bgs_conv3x3_c3_next_fused_nhwc_f32_bfx(const float* x, const void* w2split, 
                                            int N, int H, int W, int Cmid, int Cout3, int relu3, int Cnext,
                                            bgs_stream_t stream);
 int bgs_conv3x3_c3_next_eligible(int N, int H, int W, int Cmid, int Cout3, int Cnext);
+/* ... with the block's own PROJECTION SHORTCUT (1x1 / stride 1, Cin0 -> Cout3, folded BN bias_sc; resnet.py:262-263:
+ * layer1.0's downsample) computed in the same launch in place of a residual map: the residual of pixel p is
+ * conv1x1(x0, wsc)[p] + bias_sc with x0 [N,H,W,Cin0] the block input and wsc_split = bgs_conv_bfx_split_weights of the
+ * folded filter [Cout3][Cin0] — conv3 of the tail is a conv of this very shape, and the 137.6 MB map the shortcut launch
+ * stored had this launch as its one reader.  Cnext = 64: h as in bgs_conv3x3_c3_next_fused_nhwc_f32_bfx; Cnext = 0: no
+ * next conv1 (w1n_split, bias1n, h: NULL).  Forward only, frozen filters.  Supported: Cin0 = Cmid = 64, Cout3 = 256,
+ * Cnext = 0 | 64, every map size (bgs_conv3x3_c3_sc_eligible: host logic only); BGS_ERR_UNSUPPORTED otherwise.  y (and
+ * h) BIT-IDENTICAL to bgs_conv2d_nhwc_f32_bfx_ws of the shortcut with one K slice followed by the entries above: the
+ * shortcut has accumulators of its own, its k steps ascend, and (acc3 + bias3) + (acc_sc + bias_sc) is added in that order. */
+int bgs_conv3x3_c3_sc_fused_nhwc_f32_bfx(const float* x, const void* w2split, const float* bias2,
+                                         const void* w3split, const float* bias3, const float* x0,
+                                         const void* wsc_split, const float* bias_sc, float* y,
+                                         const void* w1n_split, const float* bias1n, float* h, int N, int H, int W,
+                                         int Cin0, int Cmid, int Cout3, int relu3, int Cnext, bgs_stream_t stream);
+int bgs_conv3x3_c3_sc_eligible(int N, int H, int W, int Cin0, int Cmid, int Cout3, int Cnext);
 /* The RPN head of a level in ONE launch (mmdet/models/anchor_heads/rpn_head.py:30-35): rpn_conv (3x3 / stride 1 /
  * pad 1, Cin -> 256, bias, ReLU when relu != 0) with rpn_cls + rpn_reg (one 1x1 filter [Chead][256], Chead <= 32) in its
  * epilogue — the HEAD form of the 8 x 8-pixel planes kernel (csrc/conv3x3_planes.hip), whose workgroups own all 256

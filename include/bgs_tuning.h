@@ -52,6 +52,7 @@ int bgs_selftest_mfma_peak_bf16(int blocks, int iters, int random_operands, floa
 #define BGS_CENSUS_PLANES_1X1 16      /* conv1x1_planes_bfx_kernel (A split once per K chunk into LDS planes)    */
 #define BGS_CENSUS_PLANES_3X3_HEAD 17 /* conv3x3_planes_bfx_kernel<2, true> (rpn_conv + the 1x1 RPN heads; also counted in 15) */
 #define BGS_CENSUS_FUSED_C3_NEXT 18  /* bottleneck_tail_planes_kernel<64 | 128> (the tail + the next block's conv1; also counted in 14) */
+#define BGS_CENSUS_FUSED_C3_SHORTCUT 19 /* bottleneck_tail_planes_kernel<0 | 64, true> (the tail + the block's own projection shortcut; also counted in 14, and in 18 with a next conv1) */
 #define BGS_CENSUS_FAMILIES 20
 int bgs_launch_census(int family, int reset);
 
@@ -148,6 +149,11 @@ int bgs_conv1x1_planes_last_launch(void);
  * BGS_BFX_PLANES3_S2=0 switches that form alone off). */
 void bgs_conv3x3_planes_enable(int mode);
 int bgs_conv3x3_planes_last_launch(void);
+/* The fused layer1 tail (csrc/bottleneck_tail_planes.hip; bgs.h: bgs_conv3x3_c3_*fused_nhwc_f32_bfx).  Environment, read at
+ * every call, every arm bit-identical: BGS_FUSED_C3=0 conv2 and conv3 as two launches | BGS_FUSED_C3_PLANES=0 the first
+ * form of the fused tail (8 x 16-pixel tiles; no NEXT / SC forms) | BGS_TAIL_NEXT_C1=0 the next block's conv1 as a launch
+ * of its own | BGS_TAIL_SHORTCUT=0 layer1.0's projection shortcut as a launch of its own (on the side stream, its map read
+ * back by the tail). */
 
 /* Row-per-workgroup GroupSoftmax loss kernel (csrc/gs_loss.hip, bgs_gs_loss_fwd_bwd; the bandwidth-bound form
  * of gs_bbox_head_with0.py:147-186 for N beyond the fused head's 4096 rows): prefetch 0 = every row pays its own
