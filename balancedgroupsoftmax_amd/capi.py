@@ -295,6 +295,11 @@ SIGNATURES = {
     'bgs_rcnn_targets': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32p, c_ptr,
                                         ctypes.c_int, ctypes.c_int, c_ptr, c_ptr, ctypes.c_float,
                                         c_f32p, c_ptr, c_f32p, c_f32p, c_f32p, c_ptr]),
+    'bgs_tau_norm_rows': (ctypes.c_int, [c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_f32p,
+                                         c_ptr]),
+    'bgs_score_reweight_select': (ctypes.c_int, [c_f32p, c_f32p, c_ptr, c_ptr, ctypes.c_int, ctypes.c_int, c_f32p,
+                                                 c_ptr, c_ptr]),
+    'bgs_cls_acc_count': (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int, ctypes.c_int, c_ptr, c_ptr, c_ptr]),
 }
 
 _LIB = None

@@ -56,6 +56,8 @@ class TwoStageDetector(nn.Module):
         self.bbox_roi_extractor = builder.build_roi_extractor(bbox_roi_extractor) \
             if bbox_head is not None else None
         self.bbox_head = builder.build_head(bbox_head) if bbox_head is not None else None
+        if bbox_head is not None and test_cfg is not None and test_cfg.get('test_mode', False):
+            self._build_reweight_head(bbox_head, test_cfg)
         self.mask_head = None
         if mask_head is not None:
             if mask_roi_extractor is not None:
@@ -74,6 +76,38 @@ class TwoStageDetector(nn.Module):
     with_bbox = property(lambda self: self.bbox_head is not None)
     with_mask = property(lambda self: self.mask_head is not None)
     with_shared_head = property(lambda self: False)
+
+    # -- the tau-normalised two-head test (two_stage.py:43-51; tnorm.reweight_cls_newhead fills the second head) ----
+    use_reweight = False
+    REWEIGHT_MASK = './data/lvis/mask.pt'      # the path the reference hard-codes (two_stage.py:51)
+
+    def _build_reweight_head(self, bbox_head, test_cfg):
+        """``test_cfg.test_mode``: a second head ``bbox_head_back`` from the same config (the reference's state-dict
+        keys) and the tail-class mask ``mask4newhead`` (int64 ``[num_classes]``, tools/lvis_analyse.py:270-285), read
+        from ``test_cfg.reweight_mask`` (this package's one extension; default: the reference's path).  The mask is a
+        non-persistent buffer: it follows ``.to(device)`` and, as in the reference, is no state-dict key."""
+        self.use_reweight = True
+        self.bbox_head_back = builder.build_head(bbox_head)
+        path = test_cfg.get('reweight_mask', self.REWEIGHT_MASK)
+        mask = torch.as_tensor(torch.load(path, map_location='cpu')).long().reshape(-1).contiguous()
+        if mask.numel() != self.bbox_head.num_classes:
+            raise ValueError('test_mode: %s holds %d entries, the box head has %d classes (background included)'
+                             % (path, mask.numel(), self.bbox_head.num_classes))
+        self.register_buffer('mask4newhead', mask, persistent=False)
+
+    def _reweight_mask_u8(self):
+        """``mask4newhead != 0`` as the uint8 table the select kernel reads, rebuilt when the buffer changes."""
+        m = self.mask4newhead
+        key = (id(m), m._version, m.device)
+        if self.__dict__.get('_mask_u8_key') != key:
+            self.__dict__['_mask_u8'] = (m != 0).view(torch.uint8).contiguous()
+            self.__dict__['_mask_u8_key'] = key
+        return self.__dict__['_mask_u8']
+
+    def _refuse_test_mode(self):
+        """The reference's ``aug_test`` ignores the second head and nothing in it tests several images per pass."""
+        if self.use_reweight:
+            raise NotImplementedError('test_mode: the two-head test is simple_test ground (one image, one view)')
 
     def init_weights(self, pretrained=None):
         # local checkpoint paths are loaded into the backbone, model-zoo URLs warn loudly
@@ -350,15 +384,53 @@ class TwoStageDetector(nn.Module):
         scores + decoded boxes -> one batched 1230-class NMS.  The cascades (cascade_rcnn.py:300-393,
         htc.py:313-377, ensemble result): ``_box_scores`` is their stage loop."""
         rois, valid = self._image_proposals(proposals)
-        rois, cls_score, bbox_pred = self._box_scores(x, ctx, rois, img_meta)
-        bboxes, scores = self._last_bbox_head.get_det_bboxes(
-            rois, cls_score, bbox_pred, img_meta[0]['img_shape'], img_meta[0]['scale_factor'],
-            rescale=rescale, cfg=None)
+        if self.use_reweight:
+            bboxes, scores, _ = self._reweighted_scores(x, rois, valid, img_meta, rescale)
+        else:
+            rois, cls_score, bbox_pred = self._box_scores(x, ctx, rois, img_meta)
+            bboxes, scores = self._last_bbox_head.get_det_bboxes(
+                rois, cls_score, bbox_pred, img_meta[0]['img_shape'], img_meta[0]['scale_factor'],
+                rescale=rescale, cfg=None)
         if valid is not None:        # padding rows of the fixed-shape proposal list never survive
             scores = torch.where(valid[:, None], scores, scores.new_full((), -1.0))
         det_bboxes, det_labels = PP.multiclass_nms(bboxes, scores, rcnn_test_cfg.score_thr,
                                                    rcnn_test_cfg.nms, rcnn_test_cfg.max_per_img)
         return det_bboxes, det_labels, scores
+
+    def _reweighted_scores(self, x, rois, valid, img_meta, rescale):
+        """test_mixins.py:94-130 (``simple_test_bboxes_reweight`` up to the NMS): both heads on the same RoI features,
+        ``get_det_bboxes`` of each (so a GroupSoftmax head merges its bins), then ``update_scores_with_reweight`` as ONE
+        launch writing into the first head's scores -> ``(bboxes, scores, pred_label [R] int32)``; the boxes are the
+        first head's, ``pred_label`` is the arg-max of the selected row (-1 on padding rows)."""
+        feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
+        cls_score, bbox_pred = self.bbox_head(feats, nhwc=True)
+        cls_score_rw, bbox_pred_rw = self.bbox_head_back(feats, nhwc=True)
+        shape, scale = img_meta[0]['img_shape'], img_meta[0]['scale_factor']
+        bboxes, scores = self.bbox_head.get_det_bboxes(rois, cls_score, bbox_pred, shape, scale, rescale=rescale,
+                                                       cfg=None)
+        _, scores_rw = self.bbox_head_back.get_det_bboxes(rois, cls_score_rw, bbox_pred_rw, shape, scale,
+                                                          rescale=rescale, cfg=None)
+        scores = scores.contiguous()
+        scores, pred_label = BF.score_reweight_select(scores, scores_rw, self._reweight_mask_u8(), valid=valid,
+                                                      out=scores)
+        return bboxes, scores, pred_label
+
+    def classify_proposals(self, img, img_meta, proposals=None, feats=None):
+        """What tools/test_lvis_tnorm.py:108-113 expects from the model beside the results: the image's proposals and
+        the class the two-head test gives each -> ``(proposals [R, 5], valid [R] | None, pred_label [R] int32)``, all
+        on the device; ``pred_label`` is -1 on the padding rows of the fixed-shape proposal list.  Feed them to
+        ``tnorm.ProposalAccuracy.update``."""
+        if not self.use_reweight:
+            raise RuntimeError('classify_proposals needs a model built with test_cfg.test_mode = True')
+        self._check_test_cfg()
+        with torch.no_grad():
+            x = self.extract_feat(img) if feats is None else feats
+            proposal_list = (self.simple_test_rpn(x, img_meta, self.test_cfg.rpn)
+                             if proposals is None else proposals)
+            rois, valid = self._image_proposals(proposal_list)
+            _, _, pred_label = self._reweighted_scores(x, rois, valid, img_meta, False)
+        props = proposal_list[0][0] if isinstance(proposal_list[0], tuple) else proposal_list[0]
+        return props, valid, pred_label
 
     def simple_test_mask(self, x, img_meta, det_bboxes, det_labels, rescale=False, paste=False, encode=None,
                          ctx=None):
@@ -476,6 +548,7 @@ class TwoStageDetector(nn.Module):
         ``feats``: ``extract_feat(img)`` computed ahead (``train.TrunkPipeline(inference=True)``).  ``segm='rle'``: the
         masks of all images are encoded together (``_batch_segms``)."""
         assert self.with_bbox, 'Bbox head must be implemented.'
+        self._refuse_test_mode()
         want_rle = self._check_segm(segm)
         self._check_test_cfg()
         self._check_batch(img, img_metas)
@@ -595,6 +668,7 @@ class TwoStageDetector(nn.Module):
         image scale instead of the RPN (test hook, as in ``simple_test``).  With a mask branch:
         ``(bbox_results, probs [k, 28, 28])``, or ``(bbox_results, segm_results)`` with ``segm='rle'``."""
         assert self.with_bbox, 'Bbox head must be implemented.'
+        self._refuse_test_mode()
         self._check_segm(segm)
         det_bboxes, det_labels, masks = self.aug_test_dets(imgs, img_metas, proposals, segm)
         if not rescale:
@@ -656,6 +730,9 @@ class CascadeRCNN(TwoStageDetector):
         assert bbox_roi_extractor is not None and bbox_head is not None
         if shared_head is not None:
             raise NotImplementedError('shared_head (C4 heads) is not on the BAGS path')
+        if test_cfg is not None and test_cfg.get('test_mode', False):
+            # the reference's cascades never build a second head (cascade_rcnn.py / htc.py ignore the key)
+            raise NotImplementedError('test_mode: the two-head test exists for the single-stage RoI head only')
         nn.Module.__init__(self)
         self.num_stages = num_stages
         self.backbone = builder.build_backbone(backbone)

@@ -547,6 +547,103 @@ def gs_merge_score(cls_score, pred_slice, cls2col, num_classes):
 
 
 # ----------------------------------------------------------------------------------------
+# tau-normalised two-head test  (tools/test_lvis_tnorm.py, test_mixins.py:70-92; csrc/tnorm.hip)
+# ----------------------------------------------------------------------------------------
+def _require_f32(name, **tensors):
+    for arg, t in tensors.items():
+        if t.dtype != torch.float32:
+            raise NotImplementedError('%s: %s is %s; only float32 has a kernel' % (name, arg, t.dtype))
+
+
+def _u8c(name, arg, t, n):
+    """A mask / valid vector of ``n`` entries as contiguous uint8 (non-zero = set)."""
+    if t.numel() != n:
+        raise ValueError('%s: %s has %d entries, expected %d' % (name, arg, t.numel(), n))
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    elif t.dtype != torch.uint8:
+        t = (t != 0).view(torch.uint8)
+    return t.reshape(-1).contiguous()
+
+
+def tau_normalize(weight, tau, first_row=1):
+    """``pnorm`` of ``reweight_cls_newhead`` (tools/test_lvis_tnorm.py:276-283): rows ``i >= first_row`` of
+    ``weight [C, K]`` divided by ``||row||_2 ** tau``, the rows below copied -> a new ``[C, K]`` tensor.  One launch.
+    A zero row gives NaN for ``tau > 0`` as in the reference; ``tau = 0`` returns the input bits."""
+    _require_cuda(weight)
+    _require_f32('tau_normalize', weight=weight)
+    if weight.dim() != 2:
+        raise ValueError('tau_normalize: weight must be [C, K], got %s' % (tuple(weight.shape),))
+    if int(first_row) < 0:
+        raise ValueError('tau_normalize: first_row must be >= 0')
+    lib = capi.load()
+    w = weight.detach().contiguous()
+    C, K = w.shape
+    out = torch.empty_like(w)
+    if K > 0:
+        rc = lib.bgs_tau_norm_rows(capi.ptr(w), C, K, int(first_row), float(tau), capi.ptr(out),
+                                   capi.current_stream(w.device))
+        capi.check('bgs_tau_norm_rows', rc)
+    return out
+
+
+def score_reweight_select(scores, scores_rw, mask, valid=None, out=None):
+    """``BBoxTestMixin.update_scores_with_reweight`` (test_mixins.py:70-92) in one launch, no host read:
+    a row whose chosen class (``argmax(scores)`` if that is the background, else ``argmax(scores_rw)``) is set in
+    ``mask [C]`` takes the whole row of ``scores_rw`` -> ``(out [R, C], pred_label [R] int32)`` with
+    ``pred_label = argmax(out, 1)`` (torch's CPU rule: first maximum, NaN counts as the maximum).
+    ``valid [R]``: rows with ``valid == 0`` keep ``scores`` and get ``pred_label = -1``.  ``out``: the result tensor,
+    which may be ``scores`` itself (the reference's in-place form); a fresh tensor by default."""
+    _require_cuda(scores, scores_rw, mask, valid, out)
+    _require_f32('score_reweight_select', scores=scores, scores_rw=scores_rw)
+    if scores.dim() != 2 or tuple(scores.shape) != tuple(scores_rw.shape):
+        raise ValueError('score_reweight_select: scores %s and scores_rw %s must be the same [R, C]'
+                         % (tuple(scores.shape), tuple(scores_rw.shape)))
+    R, C = scores.shape
+    if C < 1:
+        raise ValueError('score_reweight_select: no class column')
+    m = _u8c('score_reweight_select', 'mask', mask, C)
+    v = None if valid is None else _u8c('score_reweight_select', 'valid', valid, R)
+    s = scores.detach()
+    if out is None:
+        s = s.contiguous()
+        out = torch.empty_like(s)
+    else:
+        _require_f32('score_reweight_select', out=out)
+        if tuple(out.shape) != (R, C) or not out.is_contiguous() or not s.is_contiguous():
+            raise ValueError('score_reweight_select: out must be a contiguous [R, C] tensor (and scores contiguous)')
+    q = scores_rw.detach().contiguous()
+    if q.data_ptr() == out.data_ptr() and R:
+        raise ValueError('score_reweight_select: out must not be scores_rw')
+    pred = torch.empty((R,), dtype=torch.int32, device=s.device)
+    rc = capi.load().bgs_score_reweight_select(capi.ptr(s), capi.ptr(q), capi.ptr(m), capi.ptr(v), R, C,
+                                               capi.ptr(out), capi.ptr(pred), capi.current_stream(s.device))
+    capi.check('bgs_score_reweight_select', rc)
+    return out, pred
+
+
+def cls_acc_count(pred_label, assigned_label, num_ins, num_get):
+    """The counting loop of ``single_gpu_test`` (tools/test_lvis_tnorm.py:125-129) on device counters:
+    ``num_ins[g] += 1`` and ``num_get[g] += (p == g)`` for every row with ``pred_label p >= 0`` and assigned label
+    ``g`` in ``[0, C)``.  ``pred_label`` / ``assigned_label [R]`` int32, ``num_ins`` / ``num_get [C]`` int64,
+    updated in place (integer atomics: exact whatever the order) and returned."""
+    _require_cuda(pred_label, assigned_label, num_ins, num_get)
+    for arg, t in (('pred_label', pred_label), ('assigned_label', assigned_label)):
+        if t.dtype != torch.int32:
+            raise NotImplementedError('cls_acc_count: %s is %s; int32 is what the kernel reads' % (arg, t.dtype))
+    for arg, t in (('num_ins', num_ins), ('num_get', num_get)):
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError('cls_acc_count: %s must be a contiguous int64 vector' % arg)
+    if num_ins.numel() != num_get.numel() or pred_label.numel() != assigned_label.numel():
+        raise ValueError('cls_acc_count: sizes differ')
+    p, g = pred_label.reshape(-1).contiguous(), assigned_label.reshape(-1).contiguous()
+    rc = capi.load().bgs_cls_acc_count(capi.ptr(p), capi.ptr(g), p.numel(), num_ins.numel(), capi.ptr(num_ins),
+                                       capi.ptr(num_get), capi.current_stream(p.device))
+    capi.check('bgs_cls_acc_count', rc)
+    return num_ins, num_get
+
+
+# ----------------------------------------------------------------------------------------
 # box regression loss  (loss_bbox branch, :173-185)
 # ----------------------------------------------------------------------------------------
 class _BBoxSmoothL1(torch.autograd.Function):

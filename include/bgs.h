@@ -1150,6 +1150,34 @@ int bgs_sgd_clip_step(const void* const* host_params, const void* const* host_gr
                       float max_norm, float grad_scale, float lr, float momentum, float weight_decay,
                       void* workspace, size_t workspace_bytes, float* total_norm_out, bgs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * The tau-normalised two-head test (csrc/tnorm.hip).
+ *   tau_norm_rows: `pnorm` of reweight_cls_newhead (tools/test_lvis_tnorm.py:276-283, a Python loop over the rows):
+ *     w_out[i] = w_in[i] / pow(||w_in[i]||_2, tau) for i >= first_row, rows below first_row copied.  w_in / w_out
+ *     [C, K] float, any K; w_out may be w_in.  The norm is accumulated in double in a fixed order (no atomics: two
+ *     calls return the same bits) and every element is rounded once.  No guard against a zero row, as in the
+ *     reference: 0 / pow(0, tau) is NaN for tau > 0; tau = 0 returns the input bits.
+ *   score_reweight_select: BBoxTestMixin.update_scores_with_reweight (mmdet/models/detectors/test_mixins.py:70-92)
+ *     in one launch without a host read: per row a = argmax(scores[r]), b = argmax(scores_rw[r]),
+ *     cls = (a == 0) ? 0 : b,  out[r] = mask[cls] ? scores_rw[r] : scores[r],  pred_label[r] = argmax(out[r]).
+ *     The arg-max is torch's CPU rule: the first index of the maximum, a NaN counting as the maximum.
+ *     scores / scores_rw / out [R, C] float, out may be scores (the reference writes in place) but not scores_rw;
+ *     mask [C] uint8; valid [R] uint8 or NULL: a row with valid[r] == 0 (padding of the fixed-shape proposal list)
+ *     is copied from scores and gets pred_label -1; pred_label [R] int32.
+ *   cls_acc_count: the counting loop of single_gpu_test (tools/test_lvis_tnorm.py:125-129):
+ *     num_ins[assigned_label[r]] += 1, num_get[assigned_label[r]] += (pred_label[r] == assigned_label[r]) for every
+ *     row with pred_label[r] >= 0 and 0 <= assigned_label[r] < C.  num_ins / num_get [C] int64 device counters,
+ *     accumulated with integer atomics (exact, order-independent) over as many calls as the caller likes.
+ *   Zero rows is BGS_OK.
+ * ---------------------------------------------------------------------------------- */
+int bgs_tau_norm_rows(const float* w_in, int C, int K, int first_row, double tau, float* w_out,
+                      bgs_stream_t stream);
+int bgs_score_reweight_select(const float* scores, const float* scores_rw, const uint8_t* mask,
+                              const uint8_t* valid, int R, int C, float* out, int* pred_label,
+                              bgs_stream_t stream);
+int bgs_cls_acc_count(const int* pred_label, const int* assigned_label, int R, int C, long long* num_ins,
+                      long long* num_get, bgs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
