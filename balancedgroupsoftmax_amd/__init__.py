@@ -12,9 +12,10 @@ from .bbox_heads import ReweightBBoxHead
 from .config import Config, ConfigDict
 from .functional import sigmoid_focal_loss, sigmoid_focal_loss_elementwise
 from .losses import FocalLoss
-from .lvis_eval import LVISEval, LVISGroundTruth, results2json
+from .lvis_eval import LVISEval, LVISGroundTruth, ResultArrays, results2arrays, results2json
 from .ops import (DeformConv, DeformConvPack, ModulatedDeformConv, ModulatedDeformConvPack, deform_conv,
                   modulated_deform_conv)
+from .post_processing import packed2arrays
 from .pipelines import TestPipeline, TrainPipeline, rescale_size
 from .tnorm import ProposalAccuracy, reweight_cls_newhead, tail_mask
 from .registry import (BACKBONES, DETECTORS, HEADS, LOSSES, NECKS, ROI_EXTRACTORS, SHARED_HEADS,
@@ -29,4 +30,5 @@ __all__ = ['BACKBONES', 'DETECTORS', 'HEADS', 'LOSSES', 'NECKS', 'ROI_EXTRACTORS
            'TestPipeline', 'TrainPipeline', 'inference_detector', 'init_detector', 'rescale_size',
            'DeformConv', 'DeformConvPack', 'ModulatedDeformConv', 'ModulatedDeformConvPack', 'deform_conv',
            'modulated_deform_conv', 'FocalLoss', 'ReweightBBoxHead', 'sigmoid_focal_loss',
-           'sigmoid_focal_loss_elementwise', 'tnorm', 'ProposalAccuracy', 'reweight_cls_newhead', 'tail_mask']
+           'sigmoid_focal_loss_elementwise', 'tnorm', 'ProposalAccuracy', 'reweight_cls_newhead', 'tail_mask',
+           'ResultArrays', 'results2arrays', 'packed2arrays']

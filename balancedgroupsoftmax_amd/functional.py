@@ -3348,6 +3348,73 @@ def lvis_match(ious, problems, dt_area, gt_area, gt_ignore, not_exhaustive, area
     return dt_match, dt_ig, dt_bits, gt_ig
 
 
+def lvis_accumulate(dt_bits, gt_ignore, dt_score, cat_dt_off, cat_gt_off, rec_thrs, T):
+    """``LVISEval.accumulate`` (eval.py:294-422) for every category, area range and threshold in one launch
+    (``bgs_lvis_accumulate``).  ``dt_bits`` int32 ``[A, ND]`` and ``gt_ignore`` uint8 / bool ``[A, NG]`` device
+    tensors as :func:`lvis_match` returns them, ``dt_score`` fp64 ``[ND]`` device tensor; ``cat_dt_off`` /
+    ``cat_gt_off`` int64 ``[K + 1]``: category ``k`` owns detections ``cat_dt_off[k]:cat_dt_off[k + 1]`` and ground
+    truths ``cat_gt_off[k]:cat_gt_off[k + 1]`` (host arrays are checked here and uploaded; device tensors are taken
+    as they are, the kernel skips a category whose offsets leave the buffers); ``rec_thrs`` ``[R]`` host float64
+    values; ``T`` the number of threshold bits in use (A <= 4, T <= 16, R <= 256).
+    Returns device tensors ``(precision fp64 [T, R, K, A], recall fp64 [T, K, A])``, every element written.
+
+    The order of a category's detections (descending score, equal scores in the order given) is NOT computed by a
+    kernel of this package: it is the runtime's sort, two stable ``torch.sort`` calls (the negated scores ascending,
+    then the category index).  The counting and the fp64 arithmetic are ``bgs_lvis_accumulate``."""
+    import numpy as np
+    _require_cuda(dt_bits, gt_ignore, dt_score)
+    thr = np.ascontiguousarray(rec_thrs, dtype=np.float64).reshape(-1)
+    R, T = int(thr.shape[0]), int(T)
+    if dt_bits.dim() != 2 or gt_ignore.dim() != 2 or gt_ignore.shape[0] != dt_bits.shape[0]:
+        raise ValueError('lvis_accumulate: dt_bits must be [A, ND] and gt_ignore [A, NG]')
+    if dt_bits.dtype != torch.int32:
+        raise ValueError('lvis_accumulate: dt_bits must be int32 (the packed bits of lvis_match)')
+    A, ND, NG = int(dt_bits.shape[0]), int(dt_bits.shape[1]), int(gt_ignore.shape[1])
+    if tuple(dt_score.shape) != (ND,):
+        raise ValueError('lvis_accumulate: dt_score must be [ND] = [%d], got %r' % (ND, tuple(dt_score.shape)))
+    if A < 1 or T < 1 or R < 1:
+        raise ValueError('lvis_accumulate: A, T and the number of recall thresholds must be positive')
+    dev = dt_bits.device
+    offs = []
+    for o, n, what in ((cat_dt_off, ND, 'cat_dt_off'), (cat_gt_off, NG, 'cat_gt_off')):
+        if torch.is_tensor(o):
+            _require_cuda(o)
+            if o.dtype != torch.int64 or o.dim() != 1 or o.numel() < 1:
+                raise ValueError('lvis_accumulate: %s must be int64 [K + 1]' % what)
+            offs.append(o.contiguous())
+        else:
+            o = np.ascontiguousarray(o, dtype=np.int64).reshape(-1)
+            if o.size < 1 or o[0] != 0 or (np.diff(o) < 0).any() or o[-1] != n:
+                raise ValueError('lvis_accumulate: %s must start at 0, never decrease and end at %d' % (what, n))
+            offs.append(o)
+    if offs[0].shape[0] != offs[1].shape[0]:
+        raise ValueError('lvis_accumulate: cat_dt_off and cat_gt_off must both be [K + 1]')
+    K = int(offs[0].shape[0]) - 1
+    lib = capi.load()
+    # the entry's own limits, asked before any device work: with no category it validates and launches nothing
+    capi.check('bgs_lvis_accumulate', lib.bgs_lvis_accumulate(None, None, None, None, None, 0, 0, 0, A, T,
+                                                              thr.ctypes.data_as(ctypes.c_void_p), R, None, None, None))
+    with torch.cuda.device(dev):
+        if not torch.is_tensor(offs[0]) and not torch.is_tensor(offs[1]):
+            both = torch.from_numpy(np.stack(offs)).to(dev)                                # one upload
+            dt_off_d, gt_off_d = both[0], both[1]
+        else:
+            dt_off_d, gt_off_d = [o if torch.is_tensor(o) else torch.from_numpy(o).to(dev) for o in offs]
+        dt_bits = dt_bits.detach().contiguous()
+        gt_ignore = gt_ignore.detach().to(torch.uint8).contiguous()
+        score = dt_score.detach().to(torch.float64).contiguous()
+        by_score = torch.sort(-score, stable=True)[1]
+        cat = torch.searchsorted(dt_off_d[1:].contiguous(), by_score, right=True)         # the category of each
+        order = by_score[torch.sort(cat, stable=True)[1]].contiguous()
+        precision = torch.empty((T, R, K, A), dtype=torch.float64, device=dev)
+        recall = torch.empty((T, K, A), dtype=torch.float64, device=dev)
+        rc = lib.bgs_lvis_accumulate(capi.ptr(dt_bits), capi.ptr(gt_ignore), capi.ptr(order), capi.ptr(dt_off_d),
+                                     capi.ptr(gt_off_d), K, ND, NG, A, T, thr.ctypes.data_as(ctypes.c_void_p), R,
+                                     capi.ptr(precision), capi.ptr(recall), capi.current_stream(dev))
+    capi.check('bgs_lvis_accumulate', rc)
+    return precision, recall
+
+
 def mask_gt_logits(feat, weight, bias, labels):
     """``feat [P, pixels, C]``, ``weight [K, C]``, ``labels [P]`` -> ``[P, pixels]`` logits of each
     RoI's own class channel (no gradient: test-time / inspection path)."""

@@ -12,6 +12,12 @@ matchings (``functional.lvis_match``), one launch each, and sends back ten match
 range, detection); the host accumulates precision / recall per category in float64.  Match tables and
 precision / recall equal the reference's exactly (tests/golden/make_golden_lvis_eval.py executes it).
 
+Results need not be dicts: :class:`ResultArrays` holds one type's results as arrays (``results2arrays`` from the
+per-class results, ``post_processing.packed2arrays`` from the packed output of ``multiclass_nms_batched``) and
+``LVISEval`` takes it directly; a list of dicts is converted to the same arrays once and both forms share the host
+preparation.  ``LVISEval.accumulate_device()`` / ``run(accumulate='device')`` accumulate on the device
+(``functional.lvis_accumulate``, csrc/lvis_accumulate.hip), so that only precision / recall come back.
+
 Polygon ground truths (every LVIS annotation is one) become RLE on the device, all in one batch:
 ``LVISGroundTruth.rasterize_polygons()`` or ``lvis_eval(..., rasterize=True)`` (``functional.poly_rle``,
 csrc/poly_rle.hip: a restatement of pycocotools' ``rleFrPoly`` / ``rleMerge``, see tests/poly_rle_ref.py).  Without
@@ -29,7 +35,7 @@ AREA_RNG_LBL = ['all', 'small', 'medium', 'large']
 FREQ_LBL = ['r', 'c', 'f']
 
 __all__ = ['xyxy2xywh', 'det2json', 'segm2json', 'results2json', 'LVISGroundTruth', 'LVISEval', 'Params',
-           'lvis_eval']
+           'lvis_eval', 'ResultArrays', 'results2arrays']
 
 
 # ------------------------------------------------------------------ result conversion (lvis_utils.py:98-200)
@@ -104,6 +110,145 @@ def results2json(img_ids, cat_ids, results, out_file=None):
         with open(files[k], 'w') as f:
             json.dump(v, f)
     return files
+
+
+# ------------------------------------------------------------------ results as arrays
+class ResultArrays(object):
+    """The results of one type ('bbox' or 'segm') as arrays, one row per detection, in the order the list of result
+    dicts would have (first-seen image order and the order of equal scores depend on it):
+
+    ``image_id`` int64 ``[N]``, ``category_id`` int64 ``[N]``, ``score`` float64 ``[N]``, ``bbox`` float64 ``[N, 4]``
+    as ``[x, y, w, h]`` or None, ``segmentation`` a list of N RLE dicts, or the ``(counts uint32 [total], offsets
+    int64 [N + 1], sizes [N, 2])`` triple of ``functional.mask_rle_counts``, or None.
+
+    Shapes and dtypes are checked here; nothing is converted silently (a float32 score is a ``TypeError``).
+    :class:`LVISEval` takes one in place of the list of dicts; :func:`results2arrays` and
+    ``post_processing.packed2arrays`` produce them."""
+
+    def __init__(self, image_id, category_id, score, bbox=None, segmentation=None):
+        def arr(a, dtype, what):
+            a = np.asarray(a)
+            if a.dtype != dtype:
+                raise TypeError('ResultArrays: %s must be %s, got %s' % (what, np.dtype(dtype).name, a.dtype))
+            return a
+        self.image_id = arr(image_id, np.int64, 'image_id')
+        if self.image_id.ndim != 1:
+            raise ValueError('ResultArrays: image_id must be [N], got %r' % (self.image_id.shape,))
+        N = int(self.image_id.shape[0])
+        self.category_id = arr(category_id, np.int64, 'category_id')
+        self.score = arr(score, np.float64, 'score')
+        for a, what in ((self.category_id, 'category_id'), (self.score, 'score')):
+            if a.shape != (N,):
+                raise ValueError('ResultArrays: %s must be [N] = [%d], got %r' % (what, N, a.shape))
+        self.bbox = None
+        if bbox is not None:
+            self.bbox = arr(bbox, np.float64, 'bbox')
+            if self.bbox.shape != (N, 4):
+                raise ValueError('ResultArrays: bbox must be [N, 4] = [%d, 4], got %r' % (N, self.bbox.shape))
+        self.segmentation = None
+        if isinstance(segmentation, tuple):
+            if len(segmentation) != 3:
+                raise ValueError('ResultArrays: a segmentation tuple is (counts, offsets, sizes)')
+            counts = arr(segmentation[0], np.uint32, 'segmentation counts')
+            offsets = arr(segmentation[1], np.int64, 'segmentation offsets')
+            sizes = np.asarray(segmentation[2])
+            if sizes.dtype.kind not in 'iu':
+                raise TypeError('ResultArrays: segmentation sizes must be integers, got %s' % sizes.dtype)
+            if counts.ndim != 1 or offsets.shape != (N + 1,) or sizes.shape != (N, 2):
+                raise ValueError('ResultArrays: segmentation must be (counts [total], offsets [N + 1], sizes [N, 2]) '
+                                 'with N = %d, got %r, %r, %r' % (N, counts.shape, offsets.shape, sizes.shape))
+            if offsets[0] != 0 or (np.diff(offsets) < 0).any() or offsets[-1] > counts.size:
+                raise ValueError('ResultArrays: segmentation offsets must start at 0, never decrease and end inside '
+                                 'the counts')
+            self.segmentation = (np.ascontiguousarray(counts), offsets, sizes.astype(np.int64))
+        elif segmentation is not None:
+            if not isinstance(segmentation, list):
+                raise TypeError('ResultArrays: segmentation must be a list of RLE dicts or a (counts, offsets, sizes) '
+                                'tuple, got %s' % type(segmentation).__name__)
+            if len(segmentation) != N:
+                raise ValueError('ResultArrays: segmentation must hold N = %d RLE dicts, got %d'
+                                 % (N, len(segmentation)))
+            if any(not isinstance(s, dict) for s in segmentation):
+                raise TypeError('ResultArrays: every segmentation must be an RLE dict')
+            self.segmentation = segmentation
+
+    def __len__(self):
+        return int(self.image_id.shape[0])
+
+    @classmethod
+    def _from_dicts(cls, results):
+        """The list of result dicts, read once.  Not validated: a result without a ``'segmentation'`` leaves None in
+        the list and :meth:`LVISEval._prepare` refuses it where it always did."""
+        ra = cls.__new__(cls)
+        ra.image_id = np.array([r['image_id'] for r in results])
+        ra.category_id = np.array([r['category_id'] for r in results])
+        ra.score = np.array([r['score'] for r in results], dtype=np.float64)
+        ra.bbox = None
+        if 'bbox' in results[0]:
+            ra.bbox = np.array([r['bbox'] for r in results], dtype=np.float64).reshape(len(results), 4)
+        seg = [r.get('segmentation') for r in results]
+        ra.segmentation = None if all(s is None for s in seg) else seg
+        return ra
+
+
+def _per_class_rows(det):
+    """One image's per-class ``[n, 5]`` arrays -> (rows ``[k, 5]`` in label order, labels int64 ``[k]``, rows per
+    class int64 ``[C]``)."""
+    det = [_as_numpy(b) for b in det]
+    lens = np.array([b.shape[0] for b in det], dtype=np.int64)
+    labels = np.repeat(np.arange(len(det), dtype=np.int64), lens)
+    if labels.size == 0:
+        return np.zeros((0, 5), np.float32), labels, lens
+    return np.concatenate([b.reshape(-1, 5) for b in det if b.shape[0]]), labels, lens
+
+
+def _box_arrays(img, cat, rows):
+    """Rows ``[N, 5]`` (x1, y1, x2, y2, score) -> the 'bbox' :class:`ResultArrays`, with the arithmetic of
+    :func:`xyxy2xywh` on every row at once: widen to float64 first, then ``x2 - x1 + 1``."""
+    r = rows.astype(np.float64)
+    box = np.stack([r[:, 0], r[:, 1], r[:, 2] - r[:, 0] + 1, r[:, 3] - r[:, 1] + 1], axis=1)
+    return ResultArrays(img, cat, np.ascontiguousarray(r[:, 4]), bbox=box)
+
+
+def results2arrays(img_ids, cat_ids, results):
+    """:func:`results2json` without a dict per detection: the same inputs -> ``{'bbox': ResultArrays}`` or ``{'bbox':
+    ..., 'segm': ...}``, rows in exactly the order ``det2json`` / ``segm2json`` emit them (image, then label, then
+    row) and with their arithmetic (float32 widened to float64, then ``w = x2 - x1 + 1``).  The 'segm' arrays carry
+    no ``bbox`` and refer to the input's RLE dicts (``counts`` may stay ``bytes``); with ``(segms, mask_scores)`` in
+    place of ``segm_results`` the masks take their own scores."""
+    if len(results) == 0:
+        raise ValueError('results2arrays: no results')
+    with_segm = isinstance(results[0], tuple)
+    if not with_segm and not isinstance(results[0], list):
+        raise TypeError('invalid type of results')
+    cat_ids = np.asarray(cat_ids, dtype=np.int64)
+    rows, imgs, cats, segs, seg_scores = [], [], [], [], []
+    for idx, img_id in enumerate(img_ids):
+        det = results[idx][0] if with_segm else results[idx]
+        r, labels, lens = _per_class_rows(det)
+        rows.append(r)
+        imgs.append(np.full(labels.size, img_id, dtype=np.int64))
+        cats.append(cat_ids[labels])
+        if with_segm:
+            seg = results[idx][1]
+            own = isinstance(seg, tuple) and len(seg) == 2
+            masks = seg[0] if own else seg
+            present = [(int(label), int(lens[label])) for label in np.nonzero(lens)[0]]
+            for label, n in present:
+                segs.extend(masks[label][:n])
+            if own:
+                seg_scores.append(np.array([float(s) for label, n in present for s in seg[1][label][:n]],
+                                           dtype=np.float64))
+            else:
+                seg_scores.append(r[:, 4].astype(np.float64))
+    rows = np.concatenate(rows) if rows else np.zeros((0, 5), np.float32)
+    img, cat = np.concatenate(imgs), np.concatenate(cats)
+    out = {'bbox': _box_arrays(img, cat, rows)}
+    if with_segm:
+        if len(segs) != img.size:
+            raise ValueError('results2arrays: %d masks for %d boxes' % (len(segs), img.size))
+        out['segm'] = ResultArrays(img, cat, np.concatenate(seg_scores).reshape(-1), segmentation=segs)
+    return out
 
 
 # ------------------------------------------------------------------ ground truth (lvis/lvis.py)
@@ -289,9 +434,10 @@ def _take_rles(table, idx):
 
 # ------------------------------------------------------------------ the evaluator (lvis/eval.py, lvis/results.py)
 class LVISEval(object):
-    """``LVISEval(gt, results, iou_type).run()``; ``results`` is a list of result dicts (``results2json``) or the path
-    of a json file holding one.  ``evaluate()`` runs the device part, ``accumulate()`` and ``summarize()`` the host
-    part; ``eval['precision']`` is ``[10, 101, num_cats, 4]`` and ``eval['recall']`` ``[10, num_cats, 4]`` float64
+    """``LVISEval(gt, results, iou_type).run()``; ``results`` is a list of result dicts (``results2json``), the path
+    of a json file holding one, or a :class:`ResultArrays` (``results2arrays`` / ``post_processing.packed2arrays``: no
+    dict per detection).  ``evaluate()`` runs the device part, ``accumulate()`` and ``summarize()`` the host
+    part, ``accumulate_device()`` / ``run(accumulate='device')`` accumulate on the device; ``eval['precision']`` is ``[10, 101, num_cats, 4]`` and ``eval['recall']`` ``[10, num_cats, 4]`` float64
     with -1 for absent entries; ``results`` holds the 13 summary values."""
 
     def __init__(self, gt, results, iou_type='segm', max_dets=300, device=None):
@@ -301,15 +447,18 @@ class LVISEval(object):
         if isinstance(results, str):
             with open(results, 'r') as f:
                 results = json.load(f)
-        if not isinstance(results, list):
-            raise TypeError('results must be a list of dicts or the path of a json file')
+        if not isinstance(results, (list, ResultArrays)):
+            raise TypeError('results must be a list of dicts, a ResultArrays or the path of a json file')
         if len(results) == 0:
             raise ValueError('LVISEval: empty results')
         self.params = Params(iou_type, max_dets)
         self.params.img_ids = sorted(self.gt.get_img_ids())
         self.params.cat_ids = sorted(self.gt.get_cat_ids())
-        imgs = set(self.params.img_ids)
-        stray = sorted({r['image_id'] for r in results} - imgs)
+        if isinstance(results, ResultArrays):
+            stray = np.setdiff1d(results.image_id, np.asarray(self.params.img_ids, dtype=np.int64)).tolist()
+        else:
+            imgs = set(self.params.img_ids)
+            stray = sorted({r['image_id'] for r in results} - imgs)
         if stray:
             raise ValueError('LVISEval: results for image ids that are not in the ground truth: %r' % stray[:10])
         for ann in self.gt.dataset['annotations']:
@@ -324,14 +473,23 @@ class LVISEval(object):
         self.timing = OrderedDict()
         self._prep = None
         self._dt_bits = self._gt_ig = None
+        self._arrays_of = None
+        self._device_tables = None
 
     # ---- host preparation (results.py; eval.py:_prepare)
+    def _arrays(self):
+        """The results as :class:`ResultArrays`: a list of dicts is read once, here; everything after works on
+        arrays whichever form the results arrived in."""
+        if self._arrays_of is None:
+            res = self._results
+            self._arrays_of = res if isinstance(res, ResultArrays) else ResultArrays._from_dicts(res)
+        return self._arrays_of
+
     def _limit_dets_per_image(self):
-        """Indices into the result list: regrouped by image in first-seen order, images with more than ``max_dets``
+        """Row indices into the results: regrouped by image in first-seen order, images with more than ``max_dets``
         results re-sorted by descending score (stably) and cut."""
-        res = self._results
-        img = np.array([r['image_id'] for r in res])
-        score = np.array([r['score'] for r in res], dtype=np.float64)
+        ra = self._arrays()
+        img, score = ra.image_id, ra.score
         uniq, first, inv = np.unique(img, return_index=True, return_inverse=True)
         rank = np.empty(uniq.size, np.int64)
         rank[np.argsort(first, kind='stable')] = np.arange(uniq.size)           # first-seen order of the images
@@ -361,28 +519,30 @@ class LVISEval(object):
         P.img_ids = list(img_ids)
         cat_ids = np.asarray(sorted(P.cat_ids))
         n_img = int(img_ids.size)
-        res = self._results
+        ra = self._arrays()
         keep = self._limit_dets_per_image()
-        res = [res[i] for i in keep]
-        N = len(res)
+        N = int(keep.size)
         d_id = np.arange(1, N + 1, dtype=np.int64)
-        d_img = np.array([r['image_id'] for r in res])
-        d_cat = np.array([r['category_id'] for r in res])
-        d_score = np.array([r['score'] for r in res], dtype=np.float64)
+        d_img, d_cat, d_score = ra.image_id[keep], ra.category_id[keep], ra.score[keep]
         d_rle = None
-        has_box = 'bbox' in res[0]
+        seg = ra.segmentation
+
+        def kept_rles():
+            if isinstance(seg, tuple):
+                return _take_rles(seg, keep)
+            return _rle_tables([seg[i] for i in keep], 'results')
         if segm:
-            if any('segmentation' not in r for r in res):
+            if seg is None or (isinstance(seg, list) and any(seg[i] is None for i in keep)):
                 raise NotImplementedError("iou_type='segm' needs an RLE 'segmentation' in every result (box results "
                                           'would have to be rasterised as a polygon)')
-            d_rle = _rle_tables([r['segmentation'] for r in res], 'results')
-        if has_box:
-            d_box = np.array([r['bbox'] for r in res], dtype=np.float64).reshape(N, 4)
+            d_rle = kept_rles()
+        if ra.bbox is not None:
+            d_box = ra.bbox[keep]
             d_area = d_box[:, 2] * d_box[:, 3]
-        elif 'segmentation' in res[0]:
+        elif seg is not None and (isinstance(seg, tuple) or seg[keep[0]] is not None):
             d_box = None
             if d_rle is None:
-                d_rle = _rle_tables([r['segmentation'] for r in res], 'results')
+                d_rle = kept_rles()
             d_area = _rle_areas(d_rle[0], d_rle[1])
         else:
             raise ValueError("results carry neither 'bbox' nor 'segmentation'")
@@ -461,9 +621,11 @@ class LVISEval(object):
         return groups
 
     # ---- the device part
-    def evaluate(self, keep_tables=False):
+    def evaluate(self, keep_tables=False, copy_back=True):
         """IoU and matching of every problem on the device; one copy back.  ``keep_tables=True`` also fetches the IoU
-        buffer and the full match / ignore tables into ``self.tables`` (numpy; for inspection and tests)."""
+        buffer and the full match / ignore tables into ``self.tables`` (numpy; for inspection and tests).  The packed
+        match bits and the ground-truth ignore flags also stay on the device for :meth:`accumulate_device`;
+        ``copy_back=False`` leaves them there only (``accumulate()`` fetches them when it is called after all)."""
         import time
         import torch
         from . import functional as BF
@@ -510,17 +672,23 @@ class LVISEval(object):
                                                                        int(np.diff(prep['gt_off'])[p])))
             raise
         dt_match, dt_ig, dt_bits, gt_ig = out
-        A = len(self.params.area_rng)
-
-        def copy():
-            flat = torch.cat([dt_bits.reshape(-1).view(torch.uint8), gt_ig.reshape(-1)]).cpu().numpy()
-            nb = A * pr.ND * 4
-            return flat[:nb].view(np.uint32).reshape(A, pr.ND), flat[nb:].reshape(A, pr.NG).astype(bool)
-        self._dt_bits, self._gt_ig = timed('copy_s', copy)
+        self._device_tables = (dt_bits, gt_ig)
+        self._dt_bits = self._gt_ig = None
+        if copy_back or keep_tables:
+            self._dt_bits, self._gt_ig = timed('copy_s', self._fetch_match_bits)
         if keep_tables:
             self.tables = dict(ious=ious.cpu().numpy(), iou_off=pr.iou_off, dt_match=dt_match.cpu().numpy(),
                                dt_ignore=dt_ig.cpu().numpy().astype(bool), gt_ignore=self._gt_ig)
         return self
+
+    def _fetch_match_bits(self):
+        """The device tables of :meth:`evaluate` as numpy (uint32 ``[A, ND]``, bool ``[A, NG]``): one copy."""
+        import torch
+        dt_bits, gt_ig = self._device_tables
+        A, ND = dt_bits.shape
+        flat = torch.cat([dt_bits.reshape(-1).view(torch.uint8), gt_ig.reshape(-1)]).cpu().numpy()
+        nb = A * ND * 4
+        return flat[:nb].view(np.uint32).reshape(A, ND), flat[nb:].reshape(A, gt_ig.shape[1]).astype(bool)
 
     def load_match_tables(self, dt_matched, dt_ignore, gt_ignore):
         """Feed ``accumulate`` with match tables computed elsewhere, in this object's problem order
@@ -531,9 +699,12 @@ class LVISEval(object):
         w = (1 << np.arange(T, dtype=np.uint32))[None, :, None]
         self._dt_bits = ((m * w).sum(axis=1) | ((g * w).sum(axis=1) << 16)).astype(np.uint32)
         self._gt_ig = np.asarray(gt_ignore, dtype=bool)
+        self._device_tables = None
 
     # ---- accumulate (eval.py:294-422), float64 on the host, vectorised per category
     def accumulate(self):
+        if self._dt_bits is None and self._device_tables is not None:      # evaluate(copy_back=False)
+            self._dt_bits, self._gt_ig = self._fetch_match_bits()
         if self._dt_bits is None:
             raise RuntimeError('Please run evaluate() first.')
         import time
@@ -580,6 +751,39 @@ class LVISEval(object):
         self.timing['accumulate_s'] = time.perf_counter() - t0
         return self
 
+    # ---- the same on the device (functional.lvis_accumulate, csrc/lvis_accumulate.hip)
+    def accumulate_device(self):
+        """:meth:`accumulate` in one launch on the tables :meth:`evaluate` left on the device; ``precision`` and
+        ``recall`` come back in one copy and ``self.eval`` / ``self.freq_groups`` / ``self.timing['accumulate_s']``
+        are filled as :meth:`accumulate` fills them.  The order of a category's detections by score is the runtime's
+        stable sort (see ``functional.lvis_accumulate``); everything else is ``bgs_lvis_accumulate``.  Tables fed
+        through :meth:`load_match_tables` exist on the host only: ``RuntimeError``."""
+        if self._device_tables is None:
+            if self._dt_bits is not None:
+                raise RuntimeError('accumulate_device: the match tables came from load_match_tables and exist on the '
+                                   'host only; run evaluate(), or use accumulate()')
+            raise RuntimeError('Please run evaluate() first.')
+        import time
+        import torch
+        from . import functional as BF
+        t0 = time.perf_counter()
+        P, prep = self.params, self._prepare()
+        T, R, K, A = len(P.iou_thrs), len(P.rec_thrs), len(P.cat_ids), len(P.area_rng)
+        dt_bits, gt_ig = self._device_tables
+        # category k owns the problems first[k] .. first[k + 1] (category-major), hence contiguous detections and
+        # ground truths
+        first = np.searchsorted(prep['prob_cat_idx'], np.arange(K + 1), 'left')
+        score = torch.from_numpy(np.ascontiguousarray(prep['dt_score'])).to(dt_bits.device)
+        precision, recall = BF.lvis_accumulate(dt_bits, gt_ig, score, prep['dt_off'][first], prep['gt_off'][first],
+                                               P.rec_thrs, T)
+        flat = torch.cat([precision.reshape(-1), recall.reshape(-1)]).cpu().numpy()
+        n = T * R * K * A
+        self.freq_groups = self._prepare_freq_group()
+        self.eval = {'params': P, 'counts': [T, R, K, A], 'precision': flat[:n].reshape(T, R, K, A),
+                     'recall': flat[n:].reshape(T, K, A)}
+        self.timing['accumulate_s'] = time.perf_counter() - t0
+        return self
+
     def _summarize(self, kind, iou_thr=None, area_rng='all', freq_group_idx=None):
         P = self.params
         a = P.area_rng_lbl.index(area_rng)
@@ -609,9 +813,17 @@ class LVISEval(object):
             r['AR%s@%d' % (lbl[0], md)] = self._summarize('ar', area_rng=lbl)
         return self
 
-    def run(self):
-        self.evaluate()
-        self.accumulate()
+    def run(self, accumulate='host'):
+        """``evaluate`` -> ``accumulate`` -> ``summarize``.  ``accumulate='device'``: the match tables stay on the
+        device and :meth:`accumulate_device` takes the host's place; only precision / recall come back."""
+        if accumulate not in ('host', 'device'):
+            raise ValueError("run: accumulate must be 'host' or 'device', got %r" % (accumulate,))
+        if accumulate == 'device':
+            self.evaluate(copy_back=False)
+            self.accumulate_device()
+        else:
+            self.evaluate()
+            self.accumulate()
         self.summarize()
         return self
 
@@ -643,8 +855,8 @@ class LVISEval(object):
 
 def lvis_eval(results_or_files, result_types, gt, max_dets=300, device=None, rasterize=False):
     """The reference's wrapper (lvis_utils.py:16-54): for every type in ``result_types`` ('bbox', 'segm') evaluate
-    ``results_or_files[type]`` (a list of result dicts or the path of a json file: either value of ``results2json``)
-    against ``gt`` (an :class:`LVISGroundTruth`, a dataset dict or a path), print the table, and return ``{type:
+    ``results_or_files[type]`` (a list of result dicts or the path of a json file: either value of ``results2json``;
+    or a :class:`ResultArrays`: a value of ``results2arrays``) against ``gt`` (an :class:`LVISGroundTruth`, a dataset dict or a path), print the table, and return ``{type:
     results}``.  ``rasterize=True`` first converts the ground truth's polygons to RLE on the device, in place
     (:meth:`LVISGroundTruth.rasterize_polygons`): an LVIS json goes in as it is distributed."""
     for t in result_types:

@@ -200,6 +200,46 @@ def bbox2result_batched(dets, labels, counts, num_classes):
     return out
 
 
+def packed2arrays(dets, labels, counts, img_ids, cat_ids):
+    """The result of :func:`multiclass_nms_batched` -> the 'bbox' ``lvis_eval.ResultArrays`` of those images, without
+    the per-class lists and without a dict per detection.  ``dets`` / ``labels`` / ``counts`` are the tensors of one
+    batch, or three lists with one entry per batch; ``img_ids`` names the images of all batches in order and
+    ``cat_ids[label]`` is a label's category id.  ONE device-to-host copy per batch.  The rows equal
+    ``results2arrays(img_ids, cat_ids, bbox2result_batched(dets, labels, counts, len(cat_ids) + 1))['bbox']``: inside
+    an image sorted by label, stably (rows of one label keep their order); a label outside ``[0, len(cat_ids))``
+    is dropped as there."""
+    from .lvis_eval import _box_arrays
+    if torch.is_tensor(dets):
+        dets, labels, counts = [dets], [labels], [counts]
+    if not (len(dets) == len(labels) == len(counts)):
+        raise ValueError('packed2arrays: dets, labels and counts must list the same batches')
+    cat_ids = np.asarray(cat_ids, dtype=np.int64)
+    img_ids = np.asarray(img_ids, dtype=np.int64).reshape(-1)
+    C = int(cat_ids.size)
+    rows, imgs, cats = [], [], []
+    first = 0
+    for d, lab, cnt in zip(dets, labels, counts):
+        B, max_num = lab.shape
+        if first + B > img_ids.size:
+            raise ValueError('packed2arrays: %d image ids for more than %d images' % (img_ids.size, first + B))
+        packed = torch.cat([d.detach().float().reshape(B, max_num * 5), lab.detach().to(torch.float32),
+                            cnt.detach().view(B, 1).to(torch.float32)], dim=1).cpu().numpy()
+        lab_h = packed[:, max_num * 5:max_num * 6].astype(np.int64)
+        ok = (np.arange(max_num)[None, :] < packed[:, -1:].astype(np.int64)) & (lab_h >= 0) & (lab_h < C)
+        b, slot = np.nonzero(ok)                                                 # image-major, slots ascending
+        sel = np.argsort(b * C + lab_h[b, slot], kind='stable')
+        b, slot = b[sel], slot[sel]
+        rows.append(packed[:, :max_num * 5].reshape(B, max_num, 5)[b, slot])
+        imgs.append(img_ids[first + b])
+        cats.append(cat_ids[lab_h[b, slot]])
+        first += B
+    if first != img_ids.size:
+        raise ValueError('packed2arrays: %d image ids for %d images' % (img_ids.size, first))
+    if not rows:
+        raise ValueError('packed2arrays: no batches')
+    return _box_arrays(np.concatenate(imgs), np.concatenate(cats), np.concatenate(rows))
+
+
 def bbox2result(bboxes, labels, num_classes):
     """``[k,5]`` + ``[k]`` -> list of ``num_classes - 1`` float32 arrays (transforms.py:181-199)."""
     if bboxes.shape[0] == 0:

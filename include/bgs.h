@@ -1075,6 +1075,31 @@ int bgs_lvis_match(const double* ious, const long long* dt_off, const long long*
                    const double* host_iou_thrs, int T, void* workspace, size_t workspace_bytes, int* dt_match,
                    uint8_t* dt_ignore, unsigned* dt_bits, uint8_t* gt_ignore_out, bgs_stream_t stream);
 
+/* LVIS evaluation, the step after matching (csrc/lvis_accumulate.hip): LVISEval.accumulate
+ * (lvis-api/lvis/eval.py:294-422) for every category, area range and IoU threshold in one launch.
+ * The problems are category-major, so category k owns the contiguous detections cat_dt_off[k] .. cat_dt_off[k + 1]
+ * and ground truths cat_gt_off[k] .. cat_gt_off[k + 1] (device int64 [K + 1], non-decreasing, inside [0, ND] /
+ * [0, NG]; a category whose offsets leave those ranges counts as absent).
+ *   dt_bits [A, ND] uint32 as bgs_lvis_match writes it (bit t = matched, bit 16 + t = ignored), gt_ignore [A, NG]
+ *   uint8 (its gt_ignore_out), order [ND] int64: order[cat_dt_off[k] + i] is the index (a column of dt_bits) of the
+ *   category's i-th detection by descending score, equal scores in concatenation order (np.argsort(-score,
+ *   kind='mergesort') per category, plus cat_dt_off[k]); an index outside [0, ND) counts as an ignored detection.
+ *   host_rec_thrs [R] fp64, HOST.  A <= 4, T <= 16, R <= 256: BGS_ERR_UNSUPPORTED beyond, before any launch.
+ *   K == 0 is BGS_OK.
+ * Outputs, every element written: precision [T, R, K, A] and recall [T, K, A] fp64.  Per (k, a):
+ *   num_gt = the number of g in the category with gt_ignore[a, g] == 0; num_gt == 0 (a category without a problem
+ *   included): -1 everywhere.  No detection but num_gt > 0: recall 0, precision 0.0.  Otherwise, per t, over the
+ *   detections in `order`: tp_i / fp_i = the exact integer prefix counts of matched & ~ignored / ~matched & ~ignored,
+ *   rc_i = double(tp_i) / double(num_gt), pr_i = double(tp_i) / ((double(fp_i) + double(tp_i)) + 2^-52), each a
+ *   single correctly rounded fp64 operation; pr is replaced by its running maximum from the right;
+ *   recall[t, k, a] = rc_{n-1}; precision[t, r, k, a] = pr[idx_r] with idx_r the first i with
+ *   rc_i >= host_rec_thrs[r], 0.0 when there is none.  The number of detections of a category is not capped.
+ *   All counting is integer arithmetic and no atomics are used: two calls return the same bits. */
+int bgs_lvis_accumulate(const unsigned* dt_bits, const uint8_t* gt_ignore, const long long* order,
+                        const long long* cat_dt_off, const long long* cat_gt_off, int K, long long ND, long long NG,
+                        int A, int T, const double* host_rec_thrs, int R, double* precision, double* recall,
+                        bgs_stream_t stream);
+
 /* Polygon ground truths as COCO run lengths (csrc/poly_rle.hip): rleFrPoly + rleMerge of pycocotools' maskApi.c
  * (mask.frPyObjects then mask.merge, as LoadAnnotations._poly2mask and LVIS.ann_to_rle call them) for all objects of a
  * batch, in a number of launches that does not depend on the batch.  The arithmetic contract is the restatement in
