@@ -105,6 +105,7 @@ SIGNATURES = {
     'bgs_conv3x3_halo_bfx_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 5),
     'bgs_conv3x3_c3_fused_nhwc_f32_bfx': (ctypes.c_int, [c_f32p, c_ptr, c_f32p, c_ptr, c_f32p, c_f32p, c_f32p]
                                           + [ctypes.c_int] * 6 + [c_ptr]),
+    'bgs_conv3x3_c3_fused_eligible': (ctypes.c_int, [ctypes.c_int] * 5),
     'bgs_conv3x3_c3_next_fused_nhwc_f32_bfx': (ctypes.c_int,
                                                [c_f32p, c_ptr, c_f32p, c_ptr, c_f32p, c_f32p, c_f32p, c_ptr, c_f32p,
                                                 c_f32p] + [ctypes.c_int] * 7 + [c_ptr]),
@@ -121,7 +122,6 @@ SIGNATURES = {
                                              + [ctypes.c_int] * 7 + [c_ptr]),
     'bgs_conv3x3_planes_head_eligible': (ctypes.c_int, [ctypes.c_int] * 6),
     'bgs_gs_loss_tuning': (None, [ctypes.c_int]),
-    'bgs_gs_head_fold': (None, [ctypes.c_int]),
     'bgs_gs_loss_wavepriv_min_rows': (None, [ctypes.c_int]),
     'bgs_gs_merge_tuning': (None, [ctypes.c_int, ctypes.c_int]),
     'bgs_conv_bfx_wide_tuning': (None, [ctypes.c_int] * 3),

@@ -1,9 +1,11 @@
 // The second half of a frozen ResNet-50 layer1 bottleneck in one launch, planes form (round 6): conv2 (3x3 / stride 1,
 // 64 -> 64, folded BN, ReLU) -> conv3 (1x1, 64 -> 256, folded BN) + residual + ReLU
-// (mmdet/models/backbones/resnet.py:239-266).  Same contract, arithmetic and results (BIT-IDENTICAL) as
-// conv3x3_c3_fused_bfx_kernel of conv_bfx.hip and as the two launches it fuses; what changes is the shape of the work:
-//   * a workgroup owns 8 x 8 output pixels (that kernel: 8 x 16): 2100 tiles of the stride-4 map on 768 slots are 2.73
-//     rounds instead of the 1.37 rounds of double-size tiles that execute as two;
+// (mmdet/models/backbones/resnet.py:239-266) — for the stride-4 map of layer1, where the two launches are an MFMA-bound
+// 3x3 conv followed by an HBM-bound 1x1 that writes the 64-channel intermediate only to read it back.  BIT-IDENTICAL to
+// those two launches (bgs_conv3x3_halo_nhwc_f32_bfx, then bgs_conv2d_nhwc_f32_bfx_ws): the same split3 of the same fp32
+// values, the k steps and the six plane products of a step in the ring kernel's order, bias, then residual, then clamp.
+//   * a workgroup owns 8 x 8 output pixels: 2100 tiles of the stride-4 map on 768 slots are 2.73 rounds (8 x 16-pixel
+//     tiles: 1.37 rounds that execute as two);
 //   * conv2's input has 64 channels in all, so its WHOLE 10 x 10 x 64 patch is loaded once (7 buffer loads per thread;
 //     outside the image: an offset past the descriptor = 0), split once into three bf16 planes in LDS
 //     ([plane][16-channel k step][patch row of 12 slots][32 B], k halves swapped on odd rows: conv3x3_planes.hip's
@@ -48,6 +50,8 @@
 //   * half 1's planes are written while half 0's tile is stored: four barriers in the epilogue, as without SC.
 // LDS 46,464 B (NEXT = 64: 49,920), no scratch memory: three workgroups per CU.  The SC = false kernels are unchanged.
 #include <stdlib.h>
+
+#include <initializer_list>
 
 #include "conv_args.h"
 #include "bfx_split.h"
@@ -590,12 +594,23 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
 
 }  // namespace
 
-// -1: not eligible (the caller runs conv3x3_c3_fused_bfx_kernel)
-int bgs_internal_bottleneck_tail_planes(const float* x, const void* w2split, const float* bias2, const void* w3split,
-                                        const float* bias3, const float* residual, float* y, int N, int H, int W,
-                                        int relu3, hipStream_t st) {
-  const long long lim = kOob;
-  if ((long long)N * H * W * 256 * 4 >= lim) return -1;
+// ---- host side: the three entry points share the eligibility rule, the pointer check and the argument fill ----
+
+// Shapes the kernel runs: the tail of a 64 -> 64 -> 256 bottleneck on a map whose largest byte offset (the 256-channel
+// output) stays below kOob, the offset the kernel uses for "outside the image": fewer than 2,080,768 pixels.  Whether a
+// map is worth one launch is the caller's decision.  (Every partial product below stays under 2^62.)
+static int tail_eligible(int N, int H, int W, int Cmid, int Cout3) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cmid != 64 || Cout3 != 256) return 0;
+  const long long lim = kOob / (256 * 4);                           // pixels
+  const long long nh = (long long)N * H;
+  return nh < lim && nh * W < lim ? 1 : 0;
+}
+
+// every pointer the kernel reads or writes in 16-byte pieces (null = absent: aligned)
+template <class... P> static bool aligned16(P... ptr) { return ((... | (uintptr_t)ptr) % 16) == 0; }
+
+static TailArgs tail_args(const float* x, const void* w2split, const float* bias2, const void* w3split,
+                          const float* bias3, const float* residual, float* y, int N, int H, int W, int relu3) {
   TailArgs g;
   g.x = x;
   g.ws2 = reinterpret_cast<const __bf16*>(w2split);
@@ -609,15 +624,53 @@ int bgs_internal_bottleneck_tail_planes(const float* x, const void* w2split, con
   g.tiles_x = (W + 7) / 8;
   g.tiles = N * g.tiles_y * g.tiles_x;
   g.chunk = (g.tiles + 7) / 8;
-  hipLaunchKernelGGL(bottleneck_tail_planes_kernel<0>, dim3((unsigned)(8 * g.chunk)), dim3(kThreads), 0, st, g);
+  return g;
+}
+
+static TailNextArgs tail_next_args(const TailArgs& g, const void* w1n_split, const float* bias1n, float* h) {
+  TailNextArgs a;
+  a.t = g;
+  a.ws1n = reinterpret_cast<const __bf16*>(w1n_split);
+  a.bias1n = bias1n;
+  a.h = h;
+  return a;
+}
+
+// one launch of instantiation <NEXT, SC> on a grid of 8 * chunk workgroups (TailArgs::chunk); counts it in
+// BGS_CENSUS_FUSED_C3 and in the form's own census slots
+template <int NEXT, bool SC>
+static int tail_launch(const typename TailArgsOf<NEXT, SC>::type& a, int chunk, bgs_stream_t stream,
+                       std::initializer_list<int> own_slots = {}) {
+  hipLaunchKernelGGL((bottleneck_tail_planes_kernel<NEXT, SC>), dim3((unsigned)(8 * chunk)), dim3(kThreads), 0,
+                     (hipStream_t)stream, a);
+  bgs_internal_census_bump(BGS_CENSUS_FUSED_C3);
+  for (int slot : own_slots) bgs_internal_census_bump(slot);
   return hipGetLastError() == hipSuccess ? BGS_OK : BGS_ERR_LAUNCH;
 }
 
-// 1 when bgs_conv3x3_c3_next_fused_nhwc_f32_bfx runs this shape (every map size: whether a map is worth one launch is
-// the caller's decision); pure host logic
+// 1 when bgs_conv3x3_c3_fused_nhwc_f32_bfx runs this shape; pure host logic
+extern "C" int bgs_conv3x3_c3_fused_eligible(int N, int H, int W, int Cmid, int Cout3) {
+  return tail_eligible(N, H, W, Cmid, Cout3);
+}
+
+// conv2 (3x3 / s1 / p1, Cmid -> Cmid, bias2, ReLU) -> conv3 (1x1, Cmid -> Cout3, bias3) + residual + ReLU in one
+// launch: x [N,H,W,Cmid], w2split / w3split = bgs_conv_bfx_split_weights of the folded filters [Cmid][9 Cmid] /
+// [Cout3][Cmid], residual [N,H,W,Cout3] or NULL, y [N,H,W,Cout3].  BGS_ERR_UNSUPPORTED where
+// bgs_conv3x3_c3_fused_eligible is 0 or a pointer is not 16-byte aligned (callers run the two launches).
+extern "C" int bgs_conv3x3_c3_fused_nhwc_f32_bfx(const float* x, const void* w2split, const float* bias2,
+                                                 const void* w3split, const float* bias3, const float* residual,
+                                                 float* y, int N, int H, int W, int Cmid, int Cout3, int relu3,
+                                                 bgs_stream_t stream) {
+  if (N <= 0 || H <= 0 || W <= 0 || !x || !w2split || !w3split || !y) return BGS_ERR_INVALID_ARG;
+  if (!tail_eligible(N, H, W, Cmid, Cout3)) return BGS_ERR_UNSUPPORTED;
+  if (!aligned16(x, w2split, w3split, y, residual, bias2, bias3)) return BGS_ERR_UNSUPPORTED;
+  const TailArgs g = tail_args(x, w2split, bias2, w3split, bias3, residual, y, N, H, W, relu3);
+  return tail_launch<0, false>(g, g.chunk, stream);
+}
+
+// 1 when bgs_conv3x3_c3_next_fused_nhwc_f32_bfx runs this shape; pure host logic
 extern "C" int bgs_conv3x3_c3_next_eligible(int N, int H, int W, int Cmid, int Cout3, int Cnext) {
-  if (N <= 0 || H <= 0 || W <= 0 || Cmid != 64 || Cout3 != 256 || (Cnext != 64 && Cnext != 128)) return 0;
-  return (long long)N * H * W * 256 * 4 < (long long)kOob ? 1 : 0;
+  return (Cnext == 64 || Cnext == 128) ? tail_eligible(N, H, W, Cmid, Cout3) : 0;
 }
 
 // bgs_conv3x3_c3_fused_nhwc_f32_bfx with the NEXT block's conv1 in its epilogue: h [N,H,W,Cnext] =
@@ -629,42 +682,17 @@ extern "C" int bgs_conv3x3_c3_next_fused_nhwc_f32_bfx(const float* x, const void
                                                       bgs_stream_t stream) {
   if (N <= 0 || H <= 0 || W <= 0 || !x || !w2split || !w3split || !y || !w1n_split || !h) return BGS_ERR_INVALID_ARG;
   if (!bgs_conv3x3_c3_next_eligible(N, H, W, Cmid, Cout3, Cnext)) return BGS_ERR_UNSUPPORTED;
-  if (((uintptr_t)x | (uintptr_t)w2split | (uintptr_t)w3split | (uintptr_t)y | (uintptr_t)residual | (uintptr_t)bias2 |
-       (uintptr_t)bias3 | (uintptr_t)w1n_split | (uintptr_t)bias1n | (uintptr_t)h) % 16 != 0)
-    return BGS_ERR_UNSUPPORTED;
-  TailNextArgs a;
-  TailArgs& g = a.t;
-  g.x = x;
-  g.ws2 = reinterpret_cast<const __bf16*>(w2split);
-  g.bias2 = bias2;
-  g.ws3 = reinterpret_cast<const __bf16*>(w3split);
-  g.bias3 = bias3;
-  g.res = residual;
-  g.y = y;
-  g.N = N; g.H = H; g.W = W; g.relu3 = relu3;
-  g.tiles_y = (H + 7) / 8;
-  g.tiles_x = (W + 7) / 8;
-  g.tiles = N * g.tiles_y * g.tiles_x;
-  g.chunk = (g.tiles + 7) / 8;
-  a.ws1n = reinterpret_cast<const __bf16*>(w1n_split);
-  a.bias1n = bias1n;
-  a.h = h;
-  const dim3 grid((unsigned)(8 * g.chunk)), block(kThreads);
-  if (Cnext == 64) hipLaunchKernelGGL(bottleneck_tail_planes_kernel<64>, grid, block, 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(bottleneck_tail_planes_kernel<128>, grid, block, 0, (hipStream_t)stream, a);
-  bgs_internal_census_bump(BGS_CENSUS_FUSED_C3);
-  bgs_internal_census_bump(BGS_CENSUS_FUSED_C3_NEXT);
-  return hipGetLastError() == hipSuccess ? BGS_OK : BGS_ERR_LAUNCH;
+  if (!aligned16(x, w2split, w3split, y, residual, bias2, bias3, w1n_split, bias1n, h)) return BGS_ERR_UNSUPPORTED;
+  const TailArgs g = tail_args(x, w2split, bias2, w3split, bias3, residual, y, N, H, W, relu3);
+  const TailNextArgs a = tail_next_args(g, w1n_split, bias1n, h);
+  return Cnext == 64 ? tail_launch<64, false>(a, g.chunk, stream, {BGS_CENSUS_FUSED_C3_NEXT})
+                     : tail_launch<128, false>(a, g.chunk, stream, {BGS_CENSUS_FUSED_C3_NEXT});
 }
 
 // 1 when bgs_conv3x3_c3_sc_fused_nhwc_f32_bfx runs this shape: the tail of a 64 -> 64 -> 256 bottleneck whose 1x1 /
 // stride-1 projection shortcut reads Cin0 = 64 channels, with or without a 64-wide next conv1; pure host logic
 extern "C" int bgs_conv3x3_c3_sc_eligible(int N, int H, int W, int Cin0, int Cmid, int Cout3, int Cnext) {
-  if (N <= 0 || H <= 0 || W <= 0 || Cin0 != 64 || Cmid != 64 || Cout3 != 256 || (Cnext != 0 && Cnext != 64)) return 0;
-  const long long lim = kOob / (256 * 4);                           // pixels; every partial product below stays under 2^62
-  const long long nh = (long long)N * H;
-  if (nh >= lim) return 0;
-  return nh * W < lim ? 1 : 0;
+  return (Cin0 == 64 && (Cnext == 0 || Cnext == 64)) ? tail_eligible(N, H, W, Cmid, Cout3) : 0;
 }
 
 // bgs_conv3x3_c3_fused_nhwc_f32_bfx / bgs_conv3x3_c3_next_fused_nhwc_f32_bfx with the residual COMPUTED in the launch:
@@ -679,43 +707,14 @@ extern "C" int bgs_conv3x3_c3_sc_fused_nhwc_f32_bfx(const float* x, const void* 
   if (N <= 0 || H <= 0 || W <= 0 || !x || !w2split || !w3split || !x0 || !wsc_split || !y) return BGS_ERR_INVALID_ARG;
   if (Cnext != 0 && (!w1n_split || !h)) return BGS_ERR_INVALID_ARG;
   if (!bgs_conv3x3_c3_sc_eligible(N, H, W, Cin0, Cmid, Cout3, Cnext)) return BGS_ERR_UNSUPPORTED;
-  if (((uintptr_t)x | (uintptr_t)w2split | (uintptr_t)w3split | (uintptr_t)y | (uintptr_t)x0 | (uintptr_t)wsc_split |
-       (uintptr_t)bias2 | (uintptr_t)bias3 | (uintptr_t)bias_sc) % 16 != 0)
-    return BGS_ERR_UNSUPPORTED;
-  if (Cnext != 0 && ((uintptr_t)w1n_split | (uintptr_t)bias1n | (uintptr_t)h) % 16 != 0) return BGS_ERR_UNSUPPORTED;
-  TailScArgs<TailNextArgs> a;
-  TailArgs& g = a.a.t;
-  g.x = x;
-  g.ws2 = reinterpret_cast<const __bf16*>(w2split);
-  g.bias2 = bias2;
-  g.ws3 = reinterpret_cast<const __bf16*>(w3split);
-  g.bias3 = bias3;
-  g.res = nullptr;
-  g.y = y;
-  g.N = N; g.H = H; g.W = W; g.relu3 = relu3;
-  g.tiles_y = (H + 7) / 8;
-  g.tiles_x = (W + 7) / 8;
-  g.tiles = N * g.tiles_y * g.tiles_x;
-  g.chunk = (g.tiles + 7) / 8;
-  a.a.ws1n = reinterpret_cast<const __bf16*>(w1n_split);
-  a.a.bias1n = bias1n;
-  a.a.h = h;
-  a.x0 = x0;
-  a.wssc = reinterpret_cast<const __bf16*>(wsc_split);
-  a.bias_sc = bias_sc;
-  const dim3 grid((unsigned)(8 * g.chunk)), block(kThreads);
+  if (!aligned16(x, w2split, w3split, y, x0, wsc_split, bias2, bias3, bias_sc)) return BGS_ERR_UNSUPPORTED;
+  if (Cnext != 0 && !aligned16(w1n_split, bias1n, h)) return BGS_ERR_UNSUPPORTED;
+  const TailArgs g = tail_args(x, w2split, bias2, w3split, bias3, nullptr, y, N, H, W, relu3);
+  const __bf16* wssc = reinterpret_cast<const __bf16*>(wsc_split);
   if (Cnext == 64) {
-    hipLaunchKernelGGL((bottleneck_tail_planes_kernel<64, true>), grid, block, 0, (hipStream_t)stream, a);
-    bgs_internal_census_bump(BGS_CENSUS_FUSED_C3_NEXT);
-  } else {
-    TailScArgs<TailArgs> a0;
-    a0.a = g;
-    a0.x0 = a.x0;
-    a0.wssc = a.wssc;
-    a0.bias_sc = a.bias_sc;
-    hipLaunchKernelGGL((bottleneck_tail_planes_kernel<0, true>), grid, block, 0, (hipStream_t)stream, a0);
+    const TailScArgs<TailNextArgs> a = {tail_next_args(g, w1n_split, bias1n, h), x0, wssc, bias_sc};
+    return tail_launch<64, true>(a, g.chunk, stream, {BGS_CENSUS_FUSED_C3_SHORTCUT, BGS_CENSUS_FUSED_C3_NEXT});
   }
-  bgs_internal_census_bump(BGS_CENSUS_FUSED_C3);
-  bgs_internal_census_bump(BGS_CENSUS_FUSED_C3_SHORTCUT);
-  return hipGetLastError() == hipSuccess ? BGS_OK : BGS_ERR_LAUNCH;
+  const TailScArgs<TailArgs> a = {g, x0, wssc, bias_sc};
+  return tail_launch<0, true>(a, g.chunk, stream, {BGS_CENSUS_FUSED_C3_SHORTCUT});
 }

@@ -377,15 +377,19 @@ __global__ __launch_bounds__(kBlock) void gs_scale_grad_kernel(float* __restrict
 // What the first version got wrong (profiles/r4h: 20 us per 1024-row launch, 4x the plain loss
 // kernel): every one of the N workgroups hashed N 64-bit keys per sampled bin with all four waves
 // and exchanged the rank through LDS + a barrier per bin.  Now:
-//   * prologue, once per workgroup: the 16-bit flag word {real, foreground in bin b} of EVERY row
-//     (8 B of label + B table gathers per row, all loads of a thread's rows in flight together)
-//     and the per-bin foreground counts by wave ballots — no LDS atomics;
+//   * prologue, once per workgroup: the 16 flag bits {real, foreground in bin b} of EVERY row
+//     (8 B of label + one LDS table lookup per row, all loads of a thread's rows in flight
+//     together), kept as BIT PLANES: a wave turns the flags of its 64 rows into one 64-bit ballot
+//     per plane (plane b = "real and foreground in bin b", plane 15 = "real") and lane p stores
+//     plane p's word, sh_pl[p][row / 64] — no LDS atomics;
+//   * the number of real rows is one popcount pass over plane 15 (lane w = word w);
 //   * the "others" decision of the workgroup's own row in bin b is taken by THE WAVE THAT OWNS
-//     BIN b (bins are independent, one wave each): the row's position among the bin's candidates
-//     (a count over the flag words below the row, one DPP wave sum) goes through the bin's keyed
-//     pseudo-random permutation of [0, n_bg) (bgs::gs_perm, wave-uniform: scalar ALU) — drawn iff
-//     the image is < k_b: exact-k sampling without a key per row, no cross-wave exchange, so a row
-//     costs the same two barriers as the plain loss kernel;
+//     BIN b (bins are independent, one wave each): the bin's foreground count and the row's
+//     position among the bin's candidates come out of ONE pass over plane b + ONE DPP wave sum
+//     (popc(F) << 16 | popc((R ^ F) & below-the-row mask)); the position goes through the bin's
+//     keyed pseudo-random permutation of [0, n_bg) (bgs::gs_perm, wave-uniform: scalar ALU) —
+//     drawn iff the image is < k_b: exact-k sampling without a key per row, no cross-wave
+//     exchange, so a row costs the same two barriers as the plain loss kernel;
 //   * closed forms as before: k_b = int(n_fg * ratio), avg_b = n_real | n_fg + k_b | 1;
 //   * the per-bin loss weights ride in the kernel arguments (coef = w / avg * loss_weight);
 //   * the box branch of the row is four lanes of the last wave.
@@ -420,12 +424,6 @@ struct GsHeadArgs {
   int R;
   float beta, box_w;
   unsigned long long* tstamps;   // debug (bgs_gs_head_debug_timestamps): [gridDim.x][8] s_memtime marks, or null
-  // round 6: the reduction of the partials INSIDE the main launch, by the workgroup that arrives last (null: the separate
-  // gs_head_reduce_kernel launch).  ticket: a zeroed device word, left zero by the last workgroup.
-  unsigned* ticket;
-  float* fold_out;               // [B + 1] loss terms
-  float* fold_total;             // [1] or null
-  uint64_t* fold_counter;        // the draw counter to advance, or null
 };
 
 // v_writelane_b32 with a run-time lane (hipcc has no builtin for it).  gfx9 VALU instructions read ONE SGPR
@@ -453,32 +451,25 @@ __device__ __forceinline__ float gs_sl1(float d, float beta, float& grad) {
   return ad - 0.5f * beta;
 }
 
-// LDS layout (dynamic): [2][wpad] rows + read slack | flags u16 [N rounded to 64] (VAR 1: 16 bit planes of
-// N / 64 64-bit words, the same bytes) | class bits u16
-// [C rounded to 8] | counts int [kWaves][MAX_BINS + 1] | box gradient float [4]
+// LDS layout (dynamic): [2][wpad] rows + read slack | 16 bit planes of N / 64 64-bit words (2 bytes per row, N
+// rounded to 64) | class bits u16 [C rounded to 8] | kHeadLdsGap unused bytes | box gradient float [4].  The gap held
+// the per-wave counters of the retired flag-word form of this kernel; it stays so that the offset of the box gradient,
+// an immediate in the kernel's code, is the one the kernel was measured with.
+constexpr size_t kHeadLdsGap = sizeof(int) * kWaves * (BGS_MAX_BINS + 1);
 __host__ __device__ inline size_t gs_head_lds_bytes(int N, int C, int wpad) {
   return sizeof(float) * (2 * (size_t)wpad + BGS_WAVE * bgs::kSweep) + 2 * (size_t)((N + 63) & ~63) +
-         2 * (size_t)((C + 7) & ~7) + sizeof(int) * kWaves * (BGS_MAX_BINS + 1) + sizeof(float) * 4;
+         2 * (size_t)((C + 7) & ~7) + kHeadLdsGap + sizeof(float) * 4;
 }
 
-// VAR 1 (round 3, `bgs_gs_head_variant`): BIT PLANES instead of per-row flag words.  The prologue turns the
-// flag words of a wave's 64 rows into one 64-bit ballot per plane (plane b = "real and foreground in bin b",
-// plane 15 = "real") and lane p of the wave stores plane p's word: sh_pl[p][row / 64].  Then the number of
-// real rows is one popcount pass over plane 15 (lane w = word w), and for a bin b both its foreground count
-// and the row's position among the bin's candidates come out of ONE pass over plane b + ONE wave sum
-// (popc(F) << 16 | popc((R ^ F) & below-the-row mask)) in the wave that owns the bin — instead of four packed
-// counter registers with a wave sum each, an LDS exchange of the per-wave counts, and a scan over the flag words
-// below the row.  Same decisions, same arithmetic behind them: bitwise the results of VAR 0.
-template <int VEC, bool WRITE_GRAD, bool BOX, int VAR>
+template <int VEC, bool WRITE_GRAD, bool BOX>
 __global__ __launch_bounds__(kBlock) void gs_head_fused_kernel(GsHeadArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int N = a.N, C = a.C, B = a.B, W = a.W, wpad = a.wpad;
-  unsigned short* sh_flags = reinterpret_cast<unsigned short*>(smem + 2 * (size_t)wpad + BGS_WAVE * bgs::kSweep);
-  unsigned long long* sh_pl = reinterpret_cast<unsigned long long*>(sh_flags);   // VAR 1: [16][NW]
+  unsigned long long* sh_pl =
+      reinterpret_cast<unsigned long long*>(smem + 2 * (size_t)wpad + BGS_WAVE * bgs::kSweep);   // [16][NW]
   const int NW = (N + 63) >> 6;
-  unsigned short* sh_cbits = sh_flags + ((N + 63) & ~63);
-  int* sh_cntw = reinterpret_cast<int*>(sh_cbits + ((C + 7) & ~7));
-  float* sh_box = reinterpret_cast<float*>(sh_cntw + kWaves * (BGS_MAX_BINS + 1));
+  unsigned short* sh_cbits = reinterpret_cast<unsigned short*>(sh_pl) + ((N + 63) & ~63);
+  float* sh_box = reinterpret_cast<float*>(reinterpret_cast<char*>(sh_cbits + ((C + 7) & ~7)) + kHeadLdsGap);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = bgs::uniform(tid >> 6);
@@ -498,9 +489,7 @@ __global__ __launch_bounds__(kBlock) void gs_head_fused_kernel(GsHeadArgs a) {
   //      derives it from label2binlabel by a coalesced sweep.  All loads are unconditional
   //      (addresses are selected, not loads: a branch around a load makes hipcc wait for it where
   //      it is issued); the labels, the table and the workgroup's first logits row are in flight
-  //      together.  Lane b <= B of every wave counts bin b over the wave's share of the rows by
-  //      ballots (b == B: real rows) — no LDS atomics.
-  int mycnt = 0;
+  //      together.
   // the workgroup's first row: its label is the OLDEST load of the kernel; the dependent gather of its bin
   // labels is issued below, behind every independent load (the label is wave-uniform, so its first use is a
   // v_readfirstlane behind an s_waitcnt: taken here, that wait was a full memory round trip in front of all
@@ -560,7 +549,6 @@ __global__ __launch_bounds__(kBlock) void gs_head_fused_kernel(GsHeadArgs a) {
   GS_MARK(1);                             // loads landed, LDS written
   __syncthreads();                        // class bits (and the first row) are in LDS
   GS_MARK(2);
-  unsigned pk[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
   // one pass = RP rows per thread (labels + row weights in registers); the first pass uses the loads of the top
   // of the kernel and is straight-line code, batches of N > kBlock * RP rows loop
   auto pass = [&](const int base, const int64_t (&yv)[RP], const float (&rwv)[RP]) {
@@ -572,41 +560,22 @@ __global__ __launch_bounds__(kBlock) void gs_head_fused_kernel(GsHeadArgs a) {
       const int64_t y = yv[i] < 0 ? 0 : (yv[i] >= C ? (int64_t)C - 1 : yv[i]);
       bits[i] = sh_cbits[(int)y];
     }
-    if constexpr (VAR == 1) {
 #pragma unroll
-      for (int i = 0; i < RP; ++i) {
-        const int r = base + tid + kBlock * i;
-        const unsigned wbits = (r < N && rwv[i] > 0.f) ? (bits[i] | 0x8000u) : 0u;
-        int lo = 0, hi = 0;                      // lane p: plane p's word of this wave's 64 rows
-        for (int p = 1; p < B; ++p) {
-          const unsigned long long m = __ballot((wbits >> p) & 1u);
-          lo = gs_writelane((int)(unsigned)m, p, lo);
-          hi = gs_writelane((int)(unsigned)(m >> 32), p, hi);
-        }
-        const unsigned long long mr = __ballot(wbits >> 15);
-        lo = gs_writelane((int)(unsigned)mr, 15, lo);
-        hi = gs_writelane((int)(unsigned)(mr >> 32), 15, hi);
-        const int w = ((base + kBlock * i) >> 6) + wave;
-        if (lane < 16 && w < NW)
-          sh_pl[lane * NW + w] = ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo;
+    for (int i = 0; i < RP; ++i) {
+      const int r = base + tid + kBlock * i;
+      const unsigned wbits = (r < N && rwv[i] > 0.f) ? (bits[i] | 0x8000u) : 0u;
+      int lo = 0, hi = 0;                      // lane p: plane p's word of this wave's 64 rows
+      for (int p = 1; p < B; ++p) {
+        const unsigned long long m = __ballot((wbits >> p) & 1u);
+        lo = gs_writelane((int)(unsigned)m, p, lo);
+        hi = gs_writelane((int)(unsigned)(m >> 32), p, hi);
       }
-    } else {
-      bool real[RP];
-#pragma unroll
-      for (int i = 0; i < RP; ++i) {
-        const int r = base + tid + kBlock * i;
-        real[i] = r < N && rwv[i] > 0.f;
-        if (r < N) sh_flags[r] = (unsigned short)(real[i] ? (bits[i] | 0x8000u) : 0u);
-      }
-      // per-thread counters, two 16-bit fields per register: bins 2 f and 2 f + 1 (a wave's share of
-      // the rows is <= 64 * 16: no carry), field 15 = real rows
-#pragma unroll
-      for (int i = 0; i < RP; ++i) {
-        const unsigned wbits = real[i] ? (bits[i] | 0x8000u) : 0u;
-#pragma unroll
-        for (int f = 0; f < 8; ++f)
-          if (2 * f < B || f == 7) pk[f] += ((wbits >> (2 * f)) & 1u) | (((wbits >> (2 * f + 1)) & 1u) << 16);
-      }
+      const unsigned long long mr = __ballot(wbits >> 15);
+      lo = gs_writelane((int)(unsigned)mr, 15, lo);
+      hi = gs_writelane((int)(unsigned)(mr >> 32), 15, hi);
+      const int w = ((base + kBlock * i) >> 6) + wave;
+      if (lane < 16 && w < NW)
+        sh_pl[lane * NW + w] = ((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo;
     }
   };
   pass(0, y0, rwv0);
@@ -622,58 +591,16 @@ __global__ __launch_bounds__(kBlock) void gs_head_fused_kernel(GsHeadArgs a) {
     }
     pass(base, yv, rwv);
   }
-  // one DPP sum per used register; lane b <= B then picks its field (b == B: the real rows, field 15)
-  if constexpr (VAR == 0) {
-    const int fsel = lane == B ? 15 : lane;
-    unsigned mine = 0u;
-#pragma unroll
-    for (int f = 0; f < 8; ++f) {
-      if (2 * f < B || f == 7) {
-        const unsigned t = (unsigned)bgs::wave_sum_i_fast((int)pk[f]);
-        if ((fsel >> 1) == f) mine = t;
-      }
-    }
-    mycnt = (int)((mine >> (16 * (fsel & 1))) & 0xffffu);
-  }
-  if (VAR == 0 && lane <= B) sh_cntw[wave * (BGS_MAX_BINS + 1) + lane] = mycnt;
-  GS_MARK(3);                             // flags + ballots done
-  __syncthreads();                        // flags, counts and the first row are in LDS
+  GS_MARK(3);                             // ballots done
+  __syncthreads();                        // planes and the first row are in LDS
   GS_MARK(4);
 
-  // lane b < B of every wave: constants of bin b (gs_prepare_kernel's mode / k / avg)
-  int my_mode = 0, my_k = 0, my_nbg = 0;  // 0 = all zero, 1 = all one, 2 = sampled
-  float my_scale = 0.f;                   // loss_weight / avg
+  // (declared at zero, then assigned: the form this kernel's code was measured in — hipcc schedules the
+  //  bin loop of the BGS_NO_DPP build differently when these two are initialised where they are declared)
   int n_real = 0;
-  unsigned long long Rw = 0ull;             // VAR 1: lane w holds word w of the "real" plane
-  if constexpr (VAR == 1) {
-    Rw = lane < NW ? sh_pl[15 * NW + lane] : 0ull;
-    n_real = bgs::wave_sum_i_fast(__popcll(Rw));
-  } else {
-#pragma unroll
-    for (int v = 0; v < kWaves; ++v) n_real += sh_cntw[v * (BGS_MAX_BINS + 1) + B];
-  }
-  if (VAR == 0 && lane < B) {
-    int n_fg = 0;
-#pragma unroll
-    for (int v = 0; v < kWaves; ++v) n_fg += sh_cntw[v * (BGS_MAX_BINS + 1) + lane];
-    const int n_bg = n_real - n_fg;
-    my_nbg = n_bg;
-    float total;
-    if (lane == 0) {
-      my_mode = 1;
-      total = (float)n_real;
-    } else if (n_fg == 0) {
-      my_mode = 0;
-      total = 0.f;
-    } else {
-      my_k = (int)((double)n_fg * a.ratio);
-      my_mode = (my_k >= n_bg) ? 1 : 2;
-      total = my_mode == 1 ? (float)n_real : (float)(n_fg + my_k);
-    }
-    const float av = fmaxf(total, 1.f);
-    my_scale = (1.f / av) * a.lw[lane];
-    if (blockIdx.x == 0 && wave == 0 && a.avg_out) a.avg_out[lane] = av;
-  }
+  unsigned long long Rw = 0ull;             // lane w holds word w of the "real" plane
+  Rw = lane < NW ? sh_pl[15 * NW + lane] : 0ull;
+  n_real = bgs::wave_sum_i_fast(__popcll(Rw));
   const float box_scale = a.box_w / fmaxf((float)n_real, 1.f);
   float lacc = 0.f, box_acc = 0.f;
 
@@ -683,13 +610,11 @@ __global__ __launch_bounds__(kBlock) void gs_head_fused_kernel(GsHeadArgs a) {
     const bool first = r == (int)blockIdx.x;
     if (!first) bgs::stage_row<VEC>(a.logits + (size_t)r * W, row, W, tid, kBlock);
     bool real_r;
-    if constexpr (VAR == 1) {
+    {
       const int wr = bgs::uniform(r >> 6);
       const unsigned rlo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)Rw, wr);
       const unsigned rhi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(Rw >> 32), wr);
       real_r = (((r & 32) ? rhi : rlo) >> (r & 31)) & 1u;
-    } else {
-      real_r = (sh_flags[r] & 0x8000u) != 0u;
     }
     int64_t yraw = yraw_first;
     int my_bl = my_bl_first;
@@ -702,71 +627,46 @@ __global__ __launch_bounds__(kBlock) void gs_head_fused_kernel(GsHeadArgs a) {
     }
     for (int b = wave; b < B; b += kWaves) {  // bins are independent: one wave each
       const int s = a.geom.start[b], n = a.geom.len[b];
+      // constants of bin b (gs_prepare_kernel's mode / k / avg): mode 0 = all zero, 1 = all one, 2 = sampled
       int mode_b;
       const int bl_b = __builtin_amdgcn_readlane(my_bl, b);
-      float w = 0.f, scale_b;
-      if constexpr (VAR == 1) {
-        // one pass over the bin's plane: foreground count and the row's candidate position together
-        int k_b = 0, nbg_b = 0;
-        unsigned pos = 0u;
-        float total;
-        if (b == 0) {
-          mode_b = 1;
-          total = (float)n_real;
-        } else {
-          const unsigned long long Fw = lane < NW ? sh_pl[b * NW + lane] : 0ull;
-          const int wr = r >> 6;
-          const unsigned long long below = (1ull << (r & 63)) - 1ull;
-          const unsigned long long msk = lane < wr ? ~0ull : (lane == wr ? below : 0ull);
-          const unsigned tot =
-              (unsigned)bgs::wave_sum_i_fast((__popcll(Fw) << 16) | __popcll((Rw ^ Fw) & msk));
-          const int n_fg = (int)(tot >> 16);
-          pos = tot & 0xffffu;
-          nbg_b = n_real - n_fg;
-          if (n_fg == 0) {
-            mode_b = 0;
-            total = 0.f;
-          } else {
-            k_b = (int)((double)n_fg * a.ratio);
-            mode_b = (k_b >= nbg_b) ? 1 : 2;
-            total = mode_b == 1 ? (float)n_real : (float)(n_fg + k_b);
-          }
-        }
-        const float av = fmaxf(total, 1.f);
-        scale_b = (1.f / av) * a.lw[b];
-        if (first && blockIdx.x == 0 && lane == 0 && a.avg_out) a.avg_out[b] = av;
-        if (real_r) {
-          if (mode_b == 1 || (mode_b == 2 && bl_b > 0)) {
-            w = 1.f;
-          } else if (mode_b == 2) {
-            const unsigned salt = bgs::gs_bin_salt(seed, (uint32_t)b);
-            w = (k_b > 0 && bgs::gs_perm(salt, pos, (unsigned)nbg_b) < (unsigned)k_b) ? 1.f : 0.f;
-          }
-        }
+      float w = 0.f;
+      int k_b = 0, nbg_b = 0;
+      unsigned pos = 0u;
+      float total;
+      if (b == 0) {
+        mode_b = 1;
+        total = (float)n_real;
       } else {
-        mode_b = __builtin_amdgcn_readlane(my_mode, b);
-        scale_b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_scale), b));
-        if (real_r) {
-          if (mode_b == 1 || (mode_b == 2 && bl_b > 0)) {
-            w = 1.f;
-          } else if (mode_b == 2) {
-            // position of the row among the bin's candidates (real, non-foreground rows) in row
-            // order, then the bin's keyed permutation of [0, n_bg): drawn iff the image is < k_b
-            const int k_b = __builtin_amdgcn_readlane(my_k, b);
-            const int nbg_b = __builtin_amdgcn_readlane(my_nbg, b);
-            int cnt = 0;
-            for (int q0 = lane; q0 < r; q0 += BGS_WAVE * 4) {
-#pragma unroll
-              for (int u = 0; u < 4; ++u) {
-                const int q = q0 + BGS_WAVE * u;
-                const unsigned f = sh_flags[q < r ? q : 0];
-                cnt += (q < r && (f & 0x8000u) && !((f >> b) & 1u)) ? 1 : 0;
-              }
-            }
-            const unsigned pos = (unsigned)bgs::wave_sum_i_fast(cnt);
-            const unsigned salt = bgs::gs_bin_salt(seed, (uint32_t)b);
-            w = (k_b > 0 && bgs::gs_perm(salt, pos, (unsigned)nbg_b) < (unsigned)k_b) ? 1.f : 0.f;
-          }
+        // one pass over the bin's plane: foreground count and the row's candidate position (among the real,
+        // non-foreground rows, in row order) together
+        const unsigned long long Fw = lane < NW ? sh_pl[b * NW + lane] : 0ull;
+        const int wr = r >> 6;
+        const unsigned long long below = (1ull << (r & 63)) - 1ull;
+        const unsigned long long msk = lane < wr ? ~0ull : (lane == wr ? below : 0ull);
+        const unsigned tot =
+            (unsigned)bgs::wave_sum_i_fast((__popcll(Fw) << 16) | __popcll((Rw ^ Fw) & msk));
+        const int n_fg = (int)(tot >> 16);
+        pos = tot & 0xffffu;
+        nbg_b = n_real - n_fg;
+        if (n_fg == 0) {
+          mode_b = 0;
+          total = 0.f;
+        } else {
+          k_b = (int)((double)n_fg * a.ratio);
+          mode_b = (k_b >= nbg_b) ? 1 : 2;
+          total = mode_b == 1 ? (float)n_real : (float)(n_fg + k_b);
+        }
+      }
+      const float av = fmaxf(total, 1.f);
+      const float scale_b = (1.f / av) * a.lw[b];     // loss_weight / avg
+      if (first && blockIdx.x == 0 && lane == 0 && a.avg_out) a.avg_out[b] = av;
+      if (real_r) {
+        if (mode_b == 1 || (mode_b == 2 && bl_b > 0)) {
+          w = 1.f;
+        } else if (mode_b == 2) {
+          const unsigned salt = bgs::gs_bin_salt(seed, (uint32_t)b);
+          w = (k_b > 0 && bgs::gs_perm(salt, pos, (unsigned)nbg_b) < (unsigned)k_b) ? 1.f : 0.f;
         }
       }
       const float coef = w * scale_b;
@@ -843,71 +743,7 @@ __global__ __launch_bounds__(kBlock) void gs_head_fused_kernel(GsHeadArgs a) {
 // real: the "real" plane is known in closed form (no ballots, no popcount pass).
 __host__ __device__ inline size_t gs_head_multi_lds_bytes(int N, int C, int wpad, int rpar) {
   return sizeof(float) * ((size_t)rpar * wpad + BGS_WAVE * bgs::kSweep) + 2 * (size_t)((N + 63) & ~63) +
-         2 * (size_t)((C + 7) & ~7) + sizeof(float) * 4 * rpar + sizeof(float) * (BGS_MAX_BINS + 2);
-}
-
-// ---- the reduction folded into the main launch (round 6) --------------------------------------------------------
-// Every workgroup publishes its partials WRITE-THROUGH (agent-scope relaxed atomic stores: `global_store ... sc1`),
-// drains them (`s_waitcnt vmcnt(0)` in every storing wave), and one lane takes a ticket (a returning agent-scope
-// atomic add).  The workgroup that draws the last ticket reads ALL partials back with agent-scope relaxed atomic
-// loads (`sc1`: served past its own L1; the producers' stores went through their L2s, so neither a fence nor an L2
-// write-back is needed — cdna_hip_programming.md, Guideline 16, form R1) and finishes exactly as
-// gs_head_reduce_kernel does: one wave per row of partials, the same lanes adding the same values in the same order,
-// one DPP sum — bitwise the two-launch result whichever workgroup happens to be last.  It then advances the draw
-// counter (every workgroup read it at its start: all of them have arrived) and zeroes the ticket for the next launch.
-__device__ __forceinline__ void gs_store_partial(float* p, float v) {
-  __hip_atomic_store(reinterpret_cast<unsigned*>(p), __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float gs_load_partial(const float* p) {
-  return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(p), __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_AGENT));
-}
-
-// all threads of the workgroup call it after their partial stores; `scratch`: BGS_MAX_BINS + 2 floats of LDS nobody
-// else touches; nwaves = waves of the workgroup; draw0 = the counter value this launch started from
-__device__ __forceinline__ void gs_head_fold_tail(const GsHeadArgs& a, int G, bool has_box, float n_real_f,
-                                                  uint64_t draw0, float* scratch, int nwaves) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int gw = bgs::uniform(tid >> 6);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's write-through stores have left
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned old = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    scratch[BGS_MAX_BINS + 1] = old == gridDim.x - 1 ? 1.f : 0.f;
-  }
-  __syncthreads();
-  if (scratch[BGS_MAX_BINS + 1] == 0.f) return;             // workgroup-uniform
-  const int B = a.B;
-  const int rows = B + (has_box ? 1 : 0);
-  for (int row = gw; row <= B; row += nwaves) {              // (gs_head_reduce_kernel: wave `row` of B + 1 waves)
-    float acc = 0.f;
-    if (row < rows) {
-      // (no index clamp: one base address + immediate offsets.  Reads past the row's end stay inside the workspace —
-      //  (B + 1) rows of G <= 2048 floats in kMaxGrid * (BGS_MAX_BINS + 1) — and are masked out of the sum.)
-      const float* src = a.partial + (size_t)row * G + lane;
-      for (int g0 = 0; g0 < G; g0 += BGS_WAVE * 16) {
-        float v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = gs_load_partial(src + g0 + BGS_WAVE * u);
-#pragma unroll
-        for (int u = 0; u < 16; ++u) acc += (g0 + lane + BGS_WAVE * u < G) ? v[u] : 0.f;
-      }
-    }
-    float sum = bgs::wave_sum(acc);
-    if (row == B && has_box) sum *= a.box_w / n_real_f;      // avg[0] = max(#real rows, 1)
-    if (lane == 0) {
-      scratch[row] = sum;
-      a.fold_out[row] = sum;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float t = 0.f;
-    for (int b = 0; b <= B; ++b) t += scratch[b];
-    if (a.fold_total) a.fold_total[0] = t;
-    if (a.fold_counter) a.fold_counter[0] = draw0 + 1ull;
-    __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+         2 * (size_t)((C + 7) & ~7) + sizeof(float) * 4 * rpar;
 }
 
 // sum over the wave of values that are zero outside lanes 0..15: four DPP steps inside row 0 (every lane of the row
@@ -960,7 +796,7 @@ __device__ __forceinline__ float gs_bin_loss_direct(const float* __restrict__ se
 }
 
 template <int VEC, bool WRITE_GRAD, bool BOX, int RPAR, bool DIRECT>
-__global__ __launch_bounds__(kBlock * RPAR, 6) void gs_head_multi_kernel(GsHeadArgs a) {   // (6 waves per SIMD: the 80 registers it had before the folded tail)
+__global__ __launch_bounds__(kBlock * RPAR, 6) void gs_head_multi_kernel(GsHeadArgs a) {   // (6 waves per SIMD: at most 80 registers)
   constexpr int T = kBlock * RPAR;
   constexpr int RP = kFusedRowsPerPass / RPAR;      // label rows per thread and pass (a pass = 1024 rows)
   static_assert(RP >= 1, "RPAR <= 4");
@@ -972,7 +808,6 @@ __global__ __launch_bounds__(kBlock * RPAR, 6) void gs_head_multi_kernel(GsHeadA
       reinterpret_cast<unsigned long long*>(smem + (size_t)RPAR * wpad + BGS_WAVE * bgs::kSweep);   // [16][NW]
   unsigned short* sh_cbits = reinterpret_cast<unsigned short*>(sh_pl) + ((N + 63) & ~63);
   float* sh_box = reinterpret_cast<float*>(sh_cbits + cpad);                                        // [RPAR][4]
-  float* sh_fold = sh_box + 4 * RPAR;               // [BGS_MAX_BINS + 2]: the folded reduction's scratch
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int gw = bgs::uniform(tid >> 6);            // wave of the workgroup
@@ -983,8 +818,7 @@ __global__ __launch_bounds__(kBlock * RPAR, 6) void gs_head_multi_kernel(GsHeadA
   const bool has_row = r < N;
   const int rc0 = has_row ? r : 0;
   uint64_t seed = a.seed;
-  const uint64_t draw0 = a.seed_offset ? a.seed_offset[0] : 0ull;
-  if (a.seed_offset) seed += 0x2545F4914F6CDD1Dull * draw0;
+  if (a.seed_offset) seed += 0x2545F4914F6CDD1Dull * a.seed_offset[0];   // device-side draw counter
   const bool all_real = a.row_weights == nullptr;
   // (a load behind a branch is waited for where it is issued: without row weights the same load reads the labels'
   //  bytes and its value is ignored)
@@ -1205,15 +1039,9 @@ __global__ __launch_bounds__(kBlock * RPAR, 6) void gs_head_multi_kernel(GsHeadA
         drow[c] = (pos_row && c == (int)slot) ? gp : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     // partials per ROW: [B + 1][N]
-    if (a.ticket) {                           // (kernel-argument uniform) write-through: read back by the last workgroup
-      if (lane < B && (lane % kWaves) == wave) gs_store_partial(a.partial + (size_t)lane * N + r, lacc);
-      if (BOX && wave == kWaves - 1 && lane == 0) gs_store_partial(a.partial + (size_t)B * N + r, box_acc);
-    } else {
-      if (lane < B && (lane % kWaves) == wave) a.partial[(size_t)lane * N + r] = lacc;
-      if (BOX && wave == kWaves - 1 && lane == 0) a.partial[(size_t)B * N + r] = box_acc;
-    }
+    if (lane < B && (lane % kWaves) == wave) a.partial[(size_t)lane * N + r] = lacc;
+    if (BOX && wave == kWaves - 1 && lane == 0) a.partial[(size_t)B * N + r] = box_acc;
   }
-  if (a.ticket) gs_head_fold_tail(a, N, BOX, fmaxf((float)n_real, 1.f), draw0, sh_fold, T / BGS_WAVE);
 }
 
 // out[b] = sum_g partial[b][g] for b < B (loss weights are already inside), out[B] = box loss
@@ -1457,56 +1285,8 @@ namespace {
 // shared launcher of the fused head kernel; returns the grid in *grid_out
 unsigned long long* g_gs_tstamps = nullptr;
 
-// Tickets of the folded reduction (gs_head_fold_tail): a small pool of zeroed device words per device, handed out
-// round-robin — two head launches in flight at once (other streams, other graphs) take different words; the last
-// workgroup of a launch leaves its word zero.  Allocated on first use; a first use under stream capture (hipMalloc is
-// not capturable) falls back to the separate reduce launch for that call.
-constexpr int kTicketPool = 64, kTicketDevices = 16;
-unsigned* g_ticket_pool[kTicketDevices] = {};
-unsigned g_ticket_next = 0;
-// bgs_gs_head_fold / BGS_GS_HEAD_FOLD: 0 (default) = the separate reduce launch | 1 = the reduction inside the main launch.
-// MEASURED (profiles/r10h_gs_head_fold_ab.txt, hipGraph replay of the whole head step, interleaved): N = 1024 16.6 us folded
-// vs 14.7 us as two launches, N = 512 15.3 vs 14.5, N = 2048 26.0 vs 24.5 — the fold LOSES 1 - 2 us: 256 - 512 arrivals on
-// one ticket word cost 3 - 4 us (the guide's `fanin` row), every workgroup drains its gradient stores before it may
-// arrive, and the last workgroup's read-back of the 24 KB of partials is a second memory round trip on the launch's only
-// path — more than the ~1.5 us launch boundary + the 4.9 us reduce kernel it replaces, whose own loads start the
-// moment the main kernel retires.  Kept as a tested, bit-identical A/B arm ("or prove by A/B why not").
-int g_head_fold = -1;
-
-bool head_fold_enabled() {
-  if (g_head_fold < 0) {
-    const char* e = getenv("BGS_GS_HEAD_FOLD");
-    g_head_fold = (e && atoi(e) != 0) ? 1 : 0;
-  }
-  return g_head_fold != 0;
-}
-
-unsigned* take_ticket(hipStream_t st) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kTicketDevices) return nullptr;
-  if (!g_ticket_pool[dev]) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    unsigned* p = nullptr;
-    if (hipMalloc(&p, sizeof(unsigned) * kTicketPool) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    if (hipMemset(p, 0, sizeof(unsigned) * kTicketPool) != hipSuccess) {
-      (void)hipGetLastError();
-      (void)hipFree(p);
-      return nullptr;
-    }
-    g_ticket_pool[dev] = p;
-  }
-  return g_ticket_pool[dev] + (g_ticket_next++ % kTicketPool);
-}
-
-// Rows per workgroup of the fused head kernel.  Every workgroup recounts the N labels (flags, per-bin
-// counts) before its first row; with R rows per workgroup that prologue is paid N / R times instead of
+// Rows per workgroup of the fused head kernel.  Every workgroup recounts the N labels (the bit planes)
+// before its first row; with R rows per workgroup that prologue is paid N / R times instead of
 // N times, against fewer workgroups to hide latency with.  0 = default; BGS_GS_HEAD_ROWS / the tuning
 // entry override (sweep: profiles/r5k_gs_head_rows_sweep.txt).
 int g_head_rows = -1;
@@ -1519,19 +1299,21 @@ int head_rows_per_wg() {
   return g_head_rows;
 }
 
-// variant of the fused head kernel: explicit (bgs_gs_head_variant / BGS_GS_HEAD_VARIANT = 0..5) or automatic — rows
+// variant of the fused head kernel: explicit (bgs_gs_head_variant / BGS_GS_HEAD_VARIANT = 1..5) or automatic — rows
 // in parallel behind one prologue wherever the per-row partials fit the workspace (N <= kMaxGrid): four per
 // workgroup once that still gives every CU a workgroup (N >= 1024), else two; beyond, one row per workgroup with bit
 // planes (profiles/r6w_gs_head_ab.txt: 10.3 / 9.7 / 7.7 / 7.7 us at N = 1024, 8.9 / 8.6 / 7.2 / 8.4 at 512,
-// 21.3 / 20.8 / 14.9 / 14.0 at 2048 for variants 0 / 1 / 2 / 3).  Direct gradient stores (variants 4 / 5) win while
-// the launch is latency-bound and lose once the store instructions count (profiles/r6z_gs_head_ab.txt: 7.43 vs 7.68 us
-// at N = 1024, 7.07 vs 7.19 at 512, 15.3 vs 13.9 at 2048): taken up to N = 1024.
+// 21.3 / 20.8 / 14.9 / 14.0 at 2048 for variants 0 / 1 / 2 / 3; 0 was the flag-word form of the one-row kernel, since
+// removed: the value now selects variant 1).  Direct gradient stores (variants 4 / 5) win while the launch is
+// latency-bound and lose once the store instructions count (profiles/r6z_gs_head_ab.txt: 7.43 vs 7.68 us at N = 1024,
+// 7.07 vs 7.19 at 512, 15.3 vs 13.9 at 2048): taken up to N = 1024.
 int g_head_variant = -2;                    // -2: not read yet, -1: automatic
 int head_variant_for(int N) {
   if (g_head_variant == -2) {
     const char* e = getenv("BGS_GS_HEAD_VARIANT");
     g_head_variant = e ? atoi(e) : -1;
     if (g_head_variant < -1 || g_head_variant > 5) g_head_variant = -1;
+    if (g_head_variant == 0) g_head_variant = 1;
   }
   int v = g_head_variant;
   if (v < 0) v = N < 1024 ? 4 : (N == 1024 ? 5 : 3);
@@ -1596,15 +1378,8 @@ int launch_gs_head(GsHeadArgs& a, const int64_t* host_pred_slice, const float* h
 #undef BGS_MULTI_LAUNCH2
     return hipGetLastError() == hipSuccess ? BGS_OK : BGS_ERR_LAUNCH;
   }
-  a.ticket = nullptr;                       // (one row per workgroup, N > 2048: the separate reduce launch)
-  const bool planes = variant >= 1;
-#define BGS_HEAD_LAUNCH(VEC_, GRAD_, BOX_)                                                              \
-  do {                                                                                                  \
-    if (planes)                                                                                         \
-      hipLaunchKernelGGL((gs_head_fused_kernel<VEC_, GRAD_, BOX_, 1>), dim3(grid), dim3(kBlock), lds, st, a); \
-    else                                                                                                \
-      hipLaunchKernelGGL((gs_head_fused_kernel<VEC_, GRAD_, BOX_, 0>), dim3(grid), dim3(kBlock), lds, st, a); \
-  } while (0)
+#define BGS_HEAD_LAUNCH(VEC_, GRAD_, BOX_) \
+  hipLaunchKernelGGL((gs_head_fused_kernel<VEC_, GRAD_, BOX_>), dim3(grid), dim3(kBlock), lds, st, a)
 #define BGS_HEAD_VEC(VEC_)                                                                        \
   do {                                                                                            \
     if (grad) { if (box) BGS_HEAD_LAUNCH(VEC_, true, true); else BGS_HEAD_LAUNCH(VEC_, true, false); }   \
@@ -1686,14 +1461,8 @@ extern "C" int bgs_gs_head_step(const float* logits, const int64_t* labels,
   a.bbox_pred = bbox_pred; a.bbox_targets = bbox_targets; a.bbox_weights = bbox_weights;
   a.dbbox = dbbox_pred; a.R = num_reg_classes; a.beta = beta; a.box_w = box_loss_weight;
   int grid = 0;
-  if (loss_out && head_fold_enabled()) {    // the reduction inside the main launch (N <= 2048: launch_gs_head keeps it)
-    a.ticket = take_ticket((hipStream_t)stream);
-    a.fold_out = loss_out;
-    a.fold_total = total_out;
-    a.fold_counter = draw_counter;
-  }
   const int rc = launch_gs_head(a, host_pred_slice, host_bin_loss_weight, (hipStream_t)stream, &grid);
-  if (rc != BGS_OK || !loss_out || a.ticket) return rc;
+  if (rc != BGS_OK || !loss_out) return rc;
   hipLaunchKernelGGL(gs_head_reduce_kernel, dim3(1), dim3((unsigned)(BGS_WAVE * (a.B + 1))), 0, (hipStream_t)stream, a.partial,
                      grid, B, bbox_pred ? 1 : 0, box_loss_weight, avg_out, loss_out, total_out,
                      draw_counter);
@@ -1719,19 +1488,16 @@ __global__ __launch_bounds__(256) void gs_class_bits_kernel(const int64_t* __res
 }  // namespace
 
 // Debug / profiling hook: when buf != NULL every later fused-head launch records 8 s_memtime marks per
-// workgroup into buf[grid][8] (kernel start, loads landed, barrier 1, flags done, barrier 2, bins done,
+// workgroup into buf[grid][8] (kernel start, loads landed, barrier 1, ballots done, barrier 2, bins done,
 // barrier 3, end); NULL switches it off (the default).  tools/gs_phase_times.py.
 extern "C" void bgs_gs_head_debug_timestamps(unsigned long long* buf) { g_gs_tstamps = buf; }
 
-extern "C" void bgs_gs_head_variant(int variant) {      // < 0: back to the default (BGS_GS_HEAD_VARIANT or automatic)
-  g_head_variant = variant < 0 ? -2 : ((variant <= 5) ? variant : 0);
+// < 0: back to the default (BGS_GS_HEAD_VARIANT or automatic); 0 (the retired flag-word form) and unknown values: 1
+extern "C" void bgs_gs_head_variant(int variant) {
+  g_head_variant = variant < 0 ? -2 : ((variant >= 1 && variant <= 5) ? variant : 1);
 }
 
 extern "C" int bgs_gs_head_variant_used(int N) { return head_variant_for(N); }
-
-// 0 (default; < 0 restores it) = the separate gs_head_reduce_kernel launch | 1 = bgs_gs_head_step reduces its partials
-// inside the main launch for N <= 2048 (the workgroup that arrives last; bitwise the two-launch result; 1 - 2 us slower)
-extern "C" void bgs_gs_head_fold(int on) { g_head_fold = on < 0 ? 0 : (on ? 1 : 0); }
 
 extern "C" void bgs_gs_head_tuning(int rows_per_workgroup) {
   g_head_rows = (rows_per_workgroup >= 0 && rows_per_workgroup <= 64) ? rows_per_workgroup : 0;

@@ -1122,7 +1122,8 @@ def set_fused_c3(on):
 def fused_c3_eligible(x, w2, w3, stride, residual):
     """conv2 -> conv3 of a frozen bottleneck in one launch (``bgs_conv3x3_c3_fused_nhwc_f32_bfx``, round 6): fp32 NHWC
     activations under the fp32-faithful arithmetic, 3x3 / stride 1, 64 -> 64 -> 256 channels (ResNet-50 layer1), the map
-    large enough for the halo kernel, nothing that needs a gradient."""
+    large enough for the halo kernel and within the fused kernel's size bound (``bgs_conv3x3_c3_fused_eligible``; a
+    larger map runs the two launches), nothing that needs a gradient."""
     env = os.environ.get('BGS_FUSED_C3')              # (read at every call: tools/step_ab.py switches it between arms)
     on = _FUSED_C3[0] if env is None else env != '0'
     return (on and _CONV_MATH[0] == 'bf16x6' and x.is_cuda and x.dtype == torch.float32 and stride == 1
@@ -1132,37 +1133,67 @@ def fused_c3_eligible(x, w2, w3, stride, residual):
             #  summation order — and a short grid gains nothing from the fusion; csrc/conv_bfx.hip halo_bfx_plan)
             and x.shape[0] * ((x.shape[1] + 7) // 8) * ((x.shape[2] + 15) // 16) >= 700
             and not (torch.is_grad_enabled() and (x.requires_grad or w2.requires_grad or w3.requires_grad or
-                                                  (residual is not None and residual.requires_grad))))
+                                                  (residual is not None and residual.requires_grad)))
+            and bool(capi.load().bgs_conv3x3_c3_fused_eligible(x.shape[0], x.shape[1], x.shape[2], 64, 256)))
+
+
+def _c3_tail(x, w2_krsc, bias2, w3_krsc, bias3, residual=None, relu3=True, out=None, w1n_krsc=None, bias1n=None,
+             x0=None, w_sc_krsc=None, bias_sc=None):
+    """The one body of the three tail wrappers below -> ``(y, h)``: the checks, the filter splits, the allocations and
+    the choice of entry point.  ``x0`` given: the projection-shortcut form (no ``residual``); ``w1n_krsc`` given: ``h``,
+    the next block's conv1 (else ``h`` is None)."""
+    _require_cuda(x, w2_krsc, bias2, w3_krsc, bias3, residual, w1n_krsc, bias1n, x0, w_sc_krsc, bias_sc)
+    lib = capi.load()
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
+    N, H, W, Cmid = x.shape
+    Cout3 = w3_krsc.shape[0]
+    Cnext = 0 if w1n_krsc is None else w1n_krsc.shape[0]
+    assert tuple(w2_krsc.shape) == (Cmid, 3, 3, Cmid) and tuple(w3_krsc.shape) == (Cout3, 1, 1, Cmid)
+    if residual is not None:
+        assert tuple(residual.shape) == (N, H, W, Cout3) and residual.is_contiguous() and residual.dtype == torch.float32
+    y = out if out is not None else torch.empty((N, H, W, Cout3), dtype=torch.float32, device=x.device)
+    w2s = bfx_split_weights(w2_krsc.view(Cmid, 9 * Cmid), cache=True)
+    w3s = bfx_split_weights(w3_krsc.view(Cout3, Cmid), cache=True)
+    h = w1s = None
+    if Cnext:
+        assert tuple(w1n_krsc.shape) == (Cnext, 1, 1, Cout3) and w1n_krsc.is_contiguous()
+        h = torch.empty((N, H, W, Cnext), dtype=torch.float32, device=x.device)
+        w1s = bfx_split_weights(w1n_krsc.view(Cnext, Cout3), cache=True)
+    relu3 = int(bool(relu3))
+    if x0 is not None:
+        Cin0 = x0.shape[3]
+        assert residual is None
+        assert tuple(x0.shape) == (N, H, W, Cin0) and x0.is_contiguous() and x0.dtype == torch.float32
+        assert tuple(w_sc_krsc.shape) == (Cout3, 1, 1, Cin0) and w_sc_krsc.is_contiguous()
+        wss = bfx_split_weights(w_sc_krsc.view(Cout3, Cin0), cache=True)
+        name = 'bgs_conv3x3_c3_sc_fused_nhwc_f32_bfx'
+        tensors = (x, w2s, bias2, w3s, bias3, x0, wss, bias_sc, y, w1s, bias1n if Cnext else None, h)
+        ints = (N, H, W, Cin0, Cmid, Cout3, relu3, Cnext)
+    elif Cnext:
+        name = 'bgs_conv3x3_c3_next_fused_nhwc_f32_bfx'
+        tensors = (x, w2s, bias2, w3s, bias3, residual, y, w1s, bias1n, h)
+        ints = (N, H, W, Cmid, Cout3, relu3, Cnext)
+    else:
+        name = 'bgs_conv3x3_c3_fused_nhwc_f32_bfx'
+        tensors = (x, w2s, bias2, w3s, bias3, residual, y)
+        ints = (N, H, W, Cmid, Cout3, relu3)
+    rc = getattr(lib, name)(*[capi.ptr(t) for t in tensors], *ints, capi.current_stream(x.device))
+    capi.check(name, rc)
+    return y, h
 
 
 def conv3x3_c3_fused_nhwc(x, w2_krsc, bias2, w3_krsc, bias3, residual=None, relu3=True, out=None):
     """``y = act(conv1x1(relu(conv3x3(x, w2) + bias2), w3) + bias3 + residual)`` in ONE launch (the second half of a frozen
     bottleneck, resnet.py:239-266); bit-identical to the two ``conv2d_nhwc`` calls it replaces."""
-    _require_cuda(x, w2_krsc, bias2, w3_krsc, bias3, residual)
-    lib = capi.load()
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
-    N, H, W, Cmid = x.shape
-    Cout3 = w3_krsc.shape[0]
-    assert tuple(w2_krsc.shape) == (Cmid, 3, 3, Cmid) and tuple(w3_krsc.shape) == (Cout3, 1, 1, Cmid)
-    if residual is not None:
-        assert tuple(residual.shape) == (N, H, W, Cout3) and residual.is_contiguous() and residual.dtype == torch.float32
-    if out is None:
-        out = torch.empty((N, H, W, Cout3), dtype=torch.float32, device=x.device)
-    w2s = bfx_split_weights(w2_krsc.view(Cmid, 9 * Cmid), cache=True)
-    w3s = bfx_split_weights(w3_krsc.view(Cout3, Cmid), cache=True)
-    rc = lib.bgs_conv3x3_c3_fused_nhwc_f32_bfx(capi.ptr(x), capi.ptr(w2s), capi.ptr(bias2), capi.ptr(w3s),
-                                               capi.ptr(bias3), capi.ptr(residual), capi.ptr(out), N, H, W, Cmid,
-                                               Cout3, int(bool(relu3)), capi.current_stream(x.device))
-    capi.check('bgs_conv3x3_c3_fused_nhwc_f32_bfx', rc)
-    return out
+    return _c3_tail(x, w2_krsc, bias2, w3_krsc, bias3, residual, relu3, out)[0]
 
 
 def fused_c3_next_eligible(x, w2, w3, stride, residual, w1n, b1n=None, stride1n=1, pad1n=0):
     """May the tail of a frozen bottleneck ALSO emit the next block's conv1 (:func:`conv3x3_c3_next_fused_nhwc`)?
     :func:`fused_c3_eligible`, and: that conv1 is 1x1 / stride 1 / no padding with 256 -> 64 or 128 channels, it is frozen
-    and nothing needs a gradient, the arithmetic is ``bf16x6`` on fp32 storage, the tail is the planes form
-    (``BGS_FUSED_C3_PLANES`` not 0).  ``BGS_TAIL_NEXT_C1=0`` (read per call): the launches of before."""
-    if os.environ.get('BGS_TAIL_NEXT_C1', '1') == '0' or os.environ.get('BGS_FUSED_C3_PLANES', '1') == '0':
+    and nothing needs a gradient, the arithmetic is ``bf16x6`` on fp32 storage.  ``BGS_TAIL_NEXT_C1=0`` (read per call):
+    the launches of before."""
+    if os.environ.get('BGS_TAIL_NEXT_C1', '1') == '0':
         return False
     if w1n is None or w1n.dim() != 4 or stride1n != 1 or pad1n != 0:
         return False
@@ -1180,26 +1211,7 @@ def conv3x3_c3_next_fused_nhwc(x, w2_krsc, bias2, w3_krsc, bias3, w1n_krsc, bias
     """:func:`conv3x3_c3_fused_nhwc` with the NEXT block's conv1 in the same launch -> ``(y, h)``,
     ``h = relu(conv1x1(y, w1n) + bias1n)`` ``[N,H,W,Cnext]``; both bit-identical to the two calls it replaces
     (``conv3x3_c3_fused_nhwc``, then ``conv2d_nhwc(y, w1n, bias1n, relu=True)``).  Forward only, frozen filters."""
-    _require_cuda(x, w2_krsc, bias2, w3_krsc, bias3, w1n_krsc, bias1n, residual)
-    lib = capi.load()
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
-    N, H, W, Cmid = x.shape
-    Cout3, Cnext = w3_krsc.shape[0], w1n_krsc.shape[0]
-    assert tuple(w2_krsc.shape) == (Cmid, 3, 3, Cmid) and tuple(w3_krsc.shape) == (Cout3, 1, 1, Cmid)
-    assert tuple(w1n_krsc.shape) == (Cnext, 1, 1, Cout3) and w1n_krsc.is_contiguous()
-    if residual is not None:
-        assert tuple(residual.shape) == (N, H, W, Cout3) and residual.is_contiguous() and residual.dtype == torch.float32
-    y = torch.empty((N, H, W, Cout3), dtype=torch.float32, device=x.device)
-    h = torch.empty((N, H, W, Cnext), dtype=torch.float32, device=x.device)
-    w2s = bfx_split_weights(w2_krsc.view(Cmid, 9 * Cmid), cache=True)
-    w3s = bfx_split_weights(w3_krsc.view(Cout3, Cmid), cache=True)
-    w1s = bfx_split_weights(w1n_krsc.view(Cnext, Cout3), cache=True)
-    rc = lib.bgs_conv3x3_c3_next_fused_nhwc_f32_bfx(capi.ptr(x), capi.ptr(w2s), capi.ptr(bias2), capi.ptr(w3s),
-                                                    capi.ptr(bias3), capi.ptr(residual), capi.ptr(y), capi.ptr(w1s),
-                                                    capi.ptr(bias1n), capi.ptr(h), N, H, W, Cmid, Cout3,
-                                                    int(bool(relu3)), Cnext, capi.current_stream(x.device))
-    capi.check('bgs_conv3x3_c3_next_fused_nhwc_f32_bfx', rc)
-    return y, h
+    return _c3_tail(x, w2_krsc, bias2, w3_krsc, bias3, residual, relu3, w1n_krsc=w1n_krsc, bias1n=bias1n)
 
 
 def fused_c3_shortcut_eligible(x0, h1_shape, w2, w3, stride, w_sc, b_sc=None, stride_sc=1):
@@ -1207,9 +1219,8 @@ def fused_c3_shortcut_eligible(x0, h1_shape, w2, w3, stride, w_sc, b_sc=None, st
     in place of reading the map a shortcut launch wrote?  ``x0``: the block input, ``h1_shape``: the shape of conv1's
     output (the tail's input; conv1 is 1x1 / stride 1, so it is known from ``x0``).  :func:`fused_c3_eligible` on that
     shape, and: the shortcut is 1x1 / stride 1 with 64 -> 256 channels, it is frozen and nothing needs a gradient, the
-    arithmetic is ``bf16x6`` on fp32 storage, the tail is the planes form (``BGS_FUSED_C3_PLANES`` not 0).
-    ``BGS_TAIL_SHORTCUT=0`` (read per call): the launches of before."""
-    if os.environ.get('BGS_TAIL_SHORTCUT', '1') == '0' or os.environ.get('BGS_FUSED_C3_PLANES', '1') == '0':
+    arithmetic is ``bf16x6`` on fp32 storage.  ``BGS_TAIL_SHORTCUT=0`` (read per call): the launches of before."""
+    if os.environ.get('BGS_TAIL_SHORTCUT', '1') == '0':
         return False
     if w_sc is None or w_sc.dim() != 4 or stride_sc != 1 or stride != 1:
         return False
@@ -1234,31 +1245,9 @@ def conv3x3_c3_sc_fused_nhwc(x, w2_krsc, bias2, w3_krsc, bias3, x0, w_sc_krsc, b
     projection shortcut on the block input ``x0`` ``[N,H,W,64]`` — computed inside the launch -> ``y``; with ``w1n_krsc``
     (the next block's conv1, 256 -> 64) -> ``(y, h)`` as :func:`conv3x3_c3_next_fused_nhwc`.  Bit-identical to
     ``conv2d_nhwc(x0, w_sc, bias_sc)`` followed by those calls.  Forward only, frozen filters."""
-    _require_cuda(x, w2_krsc, bias2, w3_krsc, bias3, x0, w_sc_krsc, bias_sc, w1n_krsc, bias1n)
-    lib = capi.load()
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
-    N, H, W, Cmid = x.shape
-    Cout3, Cin0 = w3_krsc.shape[0], x0.shape[3]
-    Cnext = 0 if w1n_krsc is None else w1n_krsc.shape[0]
-    assert tuple(w2_krsc.shape) == (Cmid, 3, 3, Cmid) and tuple(w3_krsc.shape) == (Cout3, 1, 1, Cmid)
-    assert tuple(x0.shape) == (N, H, W, Cin0) and x0.is_contiguous() and x0.dtype == torch.float32
-    assert tuple(w_sc_krsc.shape) == (Cout3, 1, 1, Cin0) and w_sc_krsc.is_contiguous()
-    y = torch.empty((N, H, W, Cout3), dtype=torch.float32, device=x.device)
-    w2s = bfx_split_weights(w2_krsc.view(Cmid, 9 * Cmid), cache=True)
-    w3s = bfx_split_weights(w3_krsc.view(Cout3, Cmid), cache=True)
-    wss = bfx_split_weights(w_sc_krsc.view(Cout3, Cin0), cache=True)
-    h = w1s = None
-    if Cnext:
-        assert tuple(w1n_krsc.shape) == (Cnext, 1, 1, Cout3) and w1n_krsc.is_contiguous()
-        h = torch.empty((N, H, W, Cnext), dtype=torch.float32, device=x.device)
-        w1s = bfx_split_weights(w1n_krsc.view(Cnext, Cout3), cache=True)
-    rc = lib.bgs_conv3x3_c3_sc_fused_nhwc_f32_bfx(capi.ptr(x), capi.ptr(w2s), capi.ptr(bias2), capi.ptr(w3s),
-                                                  capi.ptr(bias3), capi.ptr(x0), capi.ptr(wss), capi.ptr(bias_sc),
-                                                  capi.ptr(y), capi.ptr(w1s), capi.ptr(bias1n if Cnext else None),
-                                                  capi.ptr(h), N, H, W, Cin0, Cmid, Cout3, int(bool(relu3)), Cnext,
-                                                  capi.current_stream(x.device))
-    capi.check('bgs_conv3x3_c3_sc_fused_nhwc_f32_bfx', rc)
-    return (y, h) if Cnext else y
+    y, h = _c3_tail(x, w2_krsc, bias2, w3_krsc, bias3, None, relu3, w1n_krsc=w1n_krsc, bias1n=bias1n, x0=x0,
+                    w_sc_krsc=w_sc_krsc, bias_sc=bias_sc)
+    return y if h is None else (y, h)
 
 
 def rpn_head_fusion_eligible(x, w_conv, w_head):

@@ -128,7 +128,7 @@ int bgs_gs_head_loss_fused(const float* logits, const int64_t* labels, const int
  *                 *draw_counter (device uint64 or NULL), which the main kernel read as the index of
  *                 this call's "others" draw — hipGraph replays draw fresh samples with no extra launch.
  * loss_out == NULL: main kernel only (profiling hook).  Limits of bgs_gs_head_loss_fused;
- * BGS_ERR_UNSUPPORTED also when two rows + the flag words exceed the 64 KB LDS window. */
+ * BGS_ERR_UNSUPPORTED also when two rows + the flag bit planes exceed the 64 KB LDS window. */
 int bgs_gs_head_step(const float* logits, const int64_t* labels, const int64_t* label2binlabel,
                      const uint16_t* class_bin_mask, const float* row_weights,
                      const int64_t* host_pred_slice, const float* host_bin_loss_weight, int N, int C,
@@ -365,21 +365,22 @@ int bgs_conv3x3_halo_nhwc_f32_bfx_ex(const float* x, const void* wsplit, const f
  * conv2 (3x3 / stride 1 / pad 1, Cmid -> Cmid, folded BN bias2, ReLU) -> conv3 (1x1, Cmid -> Cout3, folded BN bias3)
  * + residual + ReLU (relu3).  x [N,H,W,Cmid] fp32 NHWC; w2split / w3split = bgs_conv_bfx_split_weights of the folded
  * filters viewed as [Cmid][9 Cmid] / [Cout3][Cmid]; residual [N,H,W,Cout3] or NULL; y [N,H,W,Cout3].  The 64-channel
- * intermediate never reaches HBM.  Supported: Cmid = 64, Cout3 = 256 (ResNet-50 layer1), 16-byte aligned pointers;
- * BGS_ERR_UNSUPPORTED otherwise (run the two launches).  BIT-IDENTICAL to bgs_conv3x3_halo_nhwc_f32_bfx followed by
- * bgs_conv2d_nhwc_f32_bfx_ws with the residual.  The launch is bottleneck_tail_planes_kernel (8 x 8-pixel workgroups,
- * the whole 64-channel patch staged once; csrc/bottleneck_tail_planes.hip); BGS_FUSED_C3_PLANES=0 keeps the first form
- * (conv3x3_c3_fused_bfx_kernel, 8 x 16 pixels).  Same results, bit for bit. */
+ * intermediate never reaches HBM.  Supported: Cmid = 64, Cout3 = 256 (ResNet-50 layer1), maps of fewer than 2,080,768
+ * pixels (bgs_conv3x3_c3_fused_eligible: host logic only), 16-byte aligned pointers; BGS_ERR_UNSUPPORTED otherwise (run
+ * the two launches).  BIT-IDENTICAL to bgs_conv3x3_halo_nhwc_f32_bfx followed by bgs_conv2d_nhwc_f32_bfx_ws with the
+ * residual.  The launch is bottleneck_tail_planes_kernel (8 x 8-pixel workgroups, the whole 64-channel patch staged
+ * once; csrc/bottleneck_tail_planes.hip). */
 int bgs_conv3x3_c3_fused_nhwc_f32_bfx(const float* x, const void* w2split, const float* bias2,
                                       const void* w3split, const float* bias3, const float* residual,
                                       float* y, int N, int H, int W, int Cmid, int Cout3, int relu3,
                                       bgs_stream_t stream);
+int bgs_conv3x3_c3_fused_eligible(int N, int H, int W, int Cmid, int Cout3);
 /* ... with the NEXT block's conv1 (1x1 / stride 1, Cout3 -> Cnext, folded BN bias1n, ReLU; resnet.py:220-232) in the
  * epilogue of the same launch: a workgroup of bottleneck_tail_planes_kernel holds all Cout3 channels of its 8 x 8 pixels
  * and a 1x1 conv needs no halo.  w1n_split = bgs_conv_bfx_split_weights of the folded filter [Cnext][Cout3];
  * h [N,H,W,Cnext] = relu(conv1x1(y, w1n) + bias1n).  y is stored as before (it is the next block's residual); what goes
  * away is the launch that reads it back.  Forward only, frozen filters.  Supported: Cmid = 64, Cout3 = 256, Cnext = 64 |
- * 128, every map size (bgs_conv3x3_c3_next_eligible: host logic only); BGS_ERR_UNSUPPORTED otherwise.  Both outputs
+ * 128, the same map sizes (bgs_conv3x3_c3_next_eligible: host logic only); BGS_ERR_UNSUPPORTED otherwise.  Both outputs
  * BIT-IDENTICAL to bgs_conv3x3_c3_fused_nhwc_f32_bfx followed by bgs_conv2d_nhwc_f32_bfx_ws with one K slice. */
 int bgs_conv3x3_c3_next_fused_nhwc_f32_bfx(const float* x, const void* w2split, const float* bias2,
                                            const void* w3split, const float* bias3, const float* residual,
@@ -393,7 +394,7 @@ int bgs_conv3x3_c3_next_eligible(int N, int H, int W, int Cmid, int Cout3, int C
  * folded filter [Cout3][Cin0] — conv3 of the tail is a conv of this very shape, and the 137.6 MB map the shortcut launch
  * stored had this launch as its one reader.  Cnext = 64: h as in bgs_conv3x3_c3_next_fused_nhwc_f32_bfx; Cnext = 0: no
  * next conv1 (w1n_split, bias1n, h: NULL).  Forward only, frozen filters.  Supported: Cin0 = Cmid = 64, Cout3 = 256,
- * Cnext = 0 | 64, every map size (bgs_conv3x3_c3_sc_eligible: host logic only); BGS_ERR_UNSUPPORTED otherwise.  y (and
+ * Cnext = 0 | 64, the same map sizes (bgs_conv3x3_c3_sc_eligible: host logic only); BGS_ERR_UNSUPPORTED otherwise.  y (and
  * h) BIT-IDENTICAL to bgs_conv2d_nhwc_f32_bfx_ws of the shortcut with one K slice followed by the entries above: the
  * shortcut has accumulators of its own, its k steps ascend, and (acc3 + bias3) + (acc_sc + bias_sc) is added in that order. */
 int bgs_conv3x3_c3_sc_fused_nhwc_f32_bfx(const float* x, const void* w2split, const float* bias2,

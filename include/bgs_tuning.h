@@ -47,7 +47,7 @@ int bgs_selftest_mfma_peak_bf16(int blocks, int iters, int random_operands, floa
 #define BGS_CENSUS_GS_SCALE_GRAD 11   /* gs_head_scale_grad_kernel (a non-unit upstream gradient) */
 #define BGS_CENSUS_HALO_WIDE 12       /* conv3x3_halo_bfx7_kernel (16 x 16-pixel x 128-channel units) */
 #define BGS_CENSUS_STEM_FUSED 13      /* stem_conv7x7s2_relu_maxpool_kernel (conv + ReLU + max-pool, NCHW in) */
-#define BGS_CENSUS_FUSED_C3 14        /* conv3x3_c3_fused_bfx_kernel (conv2 -> conv3 + residual + ReLU of a frozen bottleneck) */
+#define BGS_CENSUS_FUSED_C3 14        /* bottleneck_tail_planes_kernel, every form (conv2 -> conv3 + residual + ReLU of a frozen bottleneck) */
 #define BGS_CENSUS_PLANES_3X3 15      /* conv3x3_planes_bfx_kernel (8 x 8 pixels, whole reduction per workgroup) */
 #define BGS_CENSUS_PLANES_1X1 16      /* conv1x1_planes_bfx_kernel (A split once per K chunk into LDS planes)    */
 #define BGS_CENSUS_PLANES_3X3_HEAD 17 /* conv3x3_planes_bfx_kernel<2, true> (rpn_conv + the 1x1 RPN heads; also counted in 15) */
@@ -60,19 +60,13 @@ int bgs_launch_census(int family, int reset);
  * bgs_gs_head_debug_timestamps: buf != NULL (device, [2048][8] uint64) makes every later launch record 8
  *   shader-clock marks per workgroup (tools/gs_phase_times.py); NULL (default) switches it off.
  * bgs_gs_head_tuning: rows per workgroup (0 = default).
- * bgs_gs_head_variant: 0 = one row per workgroup with per-row flag words | 1 = one row per workgroup with ballot
- *   bit planes | 2 / 3 = variant 1 with 2 / 4 rows per workgroup behind one shared prologue (N <= 2048) | 4 / 5 =
+ * bgs_gs_head_variant: 1 = one row per workgroup (ballot bit planes; also what 0, the retired flag-word form, and
+ *   unknown values select) | 2 / 3 = variant 1 with 2 / 4 rows per workgroup behind one shared prologue (N <= 2048) | 4 / 5 =
  *   2 / 3 with the gradient stored by the wave that owns the bin; < 0 (default): automatic — 4 for N < 1024, 5
  *   for N = 1024, 3 up to 2048, 1 beyond.  Bitwise the same results.  bgs_gs_head_variant_used(N): the variant a
  *   launch with N rows takes. */
 void bgs_gs_head_debug_timestamps(unsigned long long* buf);
 void bgs_gs_head_tuning(int rows_per_workgroup);
-/* Round 6: bgs_gs_head_fold(1) (default 0; < 0 restores it; env BGS_GS_HEAD_FOLD=1 starts with it on): for N <= 2048
- * bgs_gs_head_step reduces its per-row partials INSIDE the main launch — the workgroup that takes the last ticket reads
- * them back and writes loss_out / total_out / the draw counter exactly as gs_head_reduce_kernel does (bitwise the
- * two-launch result): ONE launch per head step.  Measured 1 - 2 us SLOWER than the two launches (N = 1024: 16.6 vs 14.7
- * us; profiles/r10h_gs_head_fold_ab.txt), hence off by default: a tested A/B arm. */
-void bgs_gs_head_fold(int on);
 void bgs_gs_head_variant(int variant);
 int bgs_gs_head_variant_used(int N);
 
@@ -150,10 +144,9 @@ int bgs_conv1x1_planes_last_launch(void);
 void bgs_conv3x3_planes_enable(int mode);
 int bgs_conv3x3_planes_last_launch(void);
 /* The fused layer1 tail (csrc/bottleneck_tail_planes.hip; bgs.h: bgs_conv3x3_c3_*fused_nhwc_f32_bfx).  Environment, read at
- * every call, every arm bit-identical: BGS_FUSED_C3=0 conv2 and conv3 as two launches | BGS_FUSED_C3_PLANES=0 the first
- * form of the fused tail (8 x 16-pixel tiles; no NEXT / SC forms) | BGS_TAIL_NEXT_C1=0 the next block's conv1 as a launch
- * of its own | BGS_TAIL_SHORTCUT=0 layer1.0's projection shortcut as a launch of its own (on the side stream, its map read
- * back by the tail). */
+ * every call, every arm bit-identical: BGS_FUSED_C3=0 conv2 and conv3 as two launches | BGS_TAIL_NEXT_C1=0 the next
+ * block's conv1 as a launch of its own | BGS_TAIL_SHORTCUT=0 layer1.0's projection shortcut as a launch of its own (on
+ * the side stream, its map read back by the tail). */
 
 /* Row-per-workgroup GroupSoftmax loss kernel (csrc/gs_loss.hip, bgs_gs_loss_fwd_bwd; the bandwidth-bound form
  * of gs_bbox_head_with0.py:147-186 for N beyond the fused head's 4096 rows): prefetch 0 = every row pays its own

@@ -78,22 +78,43 @@ def test_head_kernel_variant_rule_is_a_host_decision():
     """``bgs_gs_head_variant_used(N)``: which fused GroupSoftmax head kernel a launch with N rows takes — rows in
     parallel behind one prologue while the per-row partials fit the workspace (N <= 2048), with direct gradient
     stores while the launch is latency-bound (N <= 1024), one row per workgroup with bit planes beyond; an explicit
-    variant is honoured where it can run and the multi-row ones fall back beyond 2048 rows; < 0 restores the
-    rule.  Pure host logic: no GPU needed."""
+    variant is honoured where it can run and the multi-row ones fall back beyond 2048 rows; 0 (the retired flag-word
+    form) and unknown values select variant 1; < 0 restores the rule.  Pure host logic: no GPU needed."""
     lib = capi.load()
     try:
         lib.bgs_gs_head_variant(-1)
         if os.environ.get('BGS_GS_HEAD_VARIANT') is None:
             assert [lib.bgs_gs_head_variant_used(n) for n in (1, 512, 1023, 1024, 1025, 2048, 2049, 4096)] == \
                 [4, 4, 4, 5, 3, 3, 1, 1]
-        for v in range(6):
+        for v in range(1, 6):
             lib.bgs_gs_head_variant(v)
             assert lib.bgs_gs_head_variant_used(1024) == v
             assert lib.bgs_gs_head_variant_used(4096) == (v if v < 2 else 1)
-        lib.bgs_gs_head_variant(17)                   # unknown: the plain kernel
-        assert lib.bgs_gs_head_variant_used(1024) == 0
+        for v in (0, 17):                             # retired / unknown: the one-row bit-plane kernel
+            lib.bgs_gs_head_variant(v)
+            assert lib.bgs_gs_head_variant_used(1024) == 1
     finally:
         lib.bgs_gs_head_variant(-1)
+
+
+def test_fused_tail_size_bound_is_one_host_rule_for_all_three_forms():
+    """``bgs_conv3x3_c3_fused_eligible`` / ``..._next_eligible`` / ``..._sc_eligible``: the fused layer1 tail runs maps
+    of fewer than 2,080,768 pixels (its byte offsets into the 256-channel output stay below the offset it uses for
+    "outside the image") with 64 -> 64 -> 256 channels, the same boundary for the plain, next-conv1 and shortcut
+    forms.  Pure host logic: no GPU needed."""
+    lib = capi.load()
+    forms = (lambda n, h, w, cm=64: lib.bgs_conv3x3_c3_fused_eligible(n, h, w, cm, 256),
+             lambda n, h, w, cm=64: lib.bgs_conv3x3_c3_next_eligible(n, h, w, cm, 256, 64),
+             lambda n, h, w, cm=64: lib.bgs_conv3x3_c3_next_eligible(n, h, w, cm, 256, 128),
+             lambda n, h, w, cm=64: lib.bgs_conv3x3_c3_sc_eligible(n, h, w, 64, cm, 256, 0),
+             lambda n, h, w, cm=64: lib.bgs_conv3x3_c3_sc_eligible(n, h, w, 64, cm, 256, 64))
+    for f in forms:
+        assert f(1, 1040, 2000) == 1
+        assert f(1, 1, 2080767) == 1 and f(2080767, 1, 1) == 1
+        assert f(1, 1, 2080768) == 0
+        assert f(1, 1040, 2001) == 0
+        assert f(31, 200, 336) == 0                   # 2,083,200 pixels: 31 images of the stride-4 map of 800 x 1344
+        assert f(1, 1040, 2000, 32) == 0
 
 
 def test_pointer_parameters_are_void_pointers_so_plain_integer_addresses_convert():

@@ -1658,7 +1658,7 @@ def test_stride2_data_gradient_parity_rows_equal_the_zero_upsampled_form(case, m
     (2, 200, 336, True, True),          # ResNet-50 layer1 at the BASELINE size (2100 tiles)
 ], ids=lambda c: 'x'.join(str(int(v)) for v in c))
 def test_fused_conv2_conv3_bottleneck_tail_is_bit_identical_to_the_two_launches(case, monkeypatch):
-    """``conv3x3_c3_fused_bfx_kernel`` (round 6): conv2 (3x3, 64 -> 64, folded BN, ReLU) -> conv3 (1x1, 64 -> 256, folded
+    """``bottleneck_tail_planes_kernel`` (round 6; the five shapes are inside ``bgs_conv3x3_c3_fused_eligible``): conv2 (3x3, 64 -> 64, folded BN, ReLU) -> conv3 (1x1, 64 -> 256, folded
     BN) + residual + ReLU of a frozen bottleneck (mmdet/models/backbones/resnet.py:239-266) in ONE launch, the 64-channel
     intermediate kept in LDS as split bf16 planes.  Every output is accumulated in the unfused kernels' order (the halo
     kernel's taps / chunks, the ring kernel's k steps and plane products, bias then residual then clamp): BIT-IDENTICAL

@@ -1,7 +1,7 @@
 """Phase times of the fused GroupSoftmax head kernel from in-kernel s_memtime marks
 (bgs_gs_head_debug_timestamps): per workgroup, averaged over the grid.  The marks live in the ONE-row-per-
-workgroup kernels (bgs_gs_head_variant 0 = flag words, 1 = bit planes; `python tools/gs_phase_times.py [variant]`,
-default 1); the multi-row kernel the library picks by default for N <= 2048 carries none."""
+workgroup kernel (bgs_gs_head_variant 1; `python tools/gs_phase_times.py [variant]`, default 1); the multi-row
+kernel the library picks by default for N <= 2048 carries none."""
 import os, sys, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from balancedgroupsoftmax_amd import capi, functional as BF
@@ -26,7 +26,7 @@ torch.cuda.synchronize()
 lib.bgs_gs_head_debug_timestamps(None)
 t = buf.cpu().numpy().reshape(2048, 8)[:n].astype(np.float64)
 t0 = t[:, 0].min()
-names = ['start', 'loads landed + LDS written', 'barrier 1', 'flags + ballots', 'barrier 2', 'bins done (wave 0)', 'barrier 3', 'end']
+names = ['start', 'loads landed + LDS written', 'barrier 1', 'ballots', 'barrier 2', 'bins done (wave 0)', 'barrier 3', 'end']
 print('marks relative to the first workgroup start (ticks of s_memtime), mean / min / max over %d workgroups' % n)
 for i, nm in enumerate(names):
     d = t[:, i] - t0
