@@ -319,7 +319,7 @@ class Bottleneck(nn.Module):
             identity = BF.conv2d_nhwc(x, f['ds'][0], f['ds'][1], stride=self.stride)   # (the tail declined conv1's output)
         if not fuse and BF.fused_c3_eligible(out, f['c2'][0], f['c3'][0], self.stride, identity):
             # frozen 64 -> 64 -> 256 block on a large map (ResNet-50 layer1): conv2 -> conv3 + residual + ReLU in one
-            # launch, the 64-channel intermediate stays in LDS (csrc/conv_bfx.hip, round 6; bit-identical)
+            # launch, the 64-channel intermediate stays in LDS (csrc/bottleneck_tail_planes.hip, round 6; bit-identical)
             if fk is not None:
                 fk.join()
             if next_c1 is not None and BF.fused_c3_next_eligible(out, f['c2'][0], f['c3'][0], self.stride, identity,

@@ -60,27 +60,6 @@ using namespace bgs_conv;
 
 namespace {
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-  const bf16x2 h = __builtin_convertvector(f32x2{a, b}, bf16x2);   // v_cvt_pk_bf16_f32 (RNE)
-  return __builtin_bit_cast(unsigned, h);
-}
-
-// x (4 consecutive k) -> three planes of 4 packed bf16 each: conv_bfx.hip's split3, verbatim
-__device__ __forceinline__ void split3p(const f32x4 v, u32x2& hi, u32x2& mid, u32x2& lo) {
-  hi = u32x2{pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3])};
-  const f32x4 r = {bfx_resid_lo(hi[0], v[0]), bfx_resid_hi(hi[0], v[1]), bfx_resid_lo(hi[1], v[2]),
-                   bfx_resid_hi(hi[1], v[3])};
-  mid = u32x2{pk_bf16(r[0], r[1]), pk_bf16(r[2], r[3])};
-  const f32x4 r2 = {bfx_resid_lo(mid[0], r[0]), bfx_resid_hi(mid[0], r[1]), bfx_resid_lo(mid[1], r[2]),
-                    bfx_resid_hi(mid[1], r[3])};
-  lo = u32x2{pk_bf16(r2[0], r2[1]), pk_bf16(r2[2], r2[3])};
-}
-
 struct TailArgs {
   const float* x;        // [N,H,W,64]
   const __bf16* ws2;     // split conv2 filter [3][36][64][16]: k step = tap * 4 + 16-channel chunk
@@ -223,7 +202,7 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
   for (int i = 0; i < AQT; ++i) {
     if (a_dst[i] < 0) continue;
     u32x2 hh, mm, ll;
-    split3p(ra[i], hh, mm, ll);
+    split3(ra[i], hh, mm, ll);
     unsigned char* d = lds + a_dst[i];
     *reinterpret_cast<u32x2*>(d) = hh;
     *reinterpret_cast<u32x2*>(d + PL) = mm;
@@ -299,7 +278,7 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
 #pragma unroll
       for (int t = 0; t < 4; ++t) v[t] = fmaxf(v[t], 0.f);
       u32x2 hh, mm, ll;
-      split3p(v, hh, mm, ll);
+      split3(v, hh, mm, ll);
       unsigned char* d = lds + Y_OFF + kc2 * P3_CH + i * 32 + (((kq2 >> 1) ^ ((i >> 3) & 1)) << 4) + (kq2 & 1) * 8;
       *reinterpret_cast<u32x2*>(d) = hh;
       *reinterpret_cast<u32x2*>(d + P3_PL) = mm;
@@ -373,7 +352,7 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
       for (int j = 0; j < 2; ++j) {
         const int i = (tid >> 4) + 16 * j;
         u32x2 hh, mm, ll;
-        split3p(rx[2 * a + j], hh, mm, ll);
+        split3(rx[2 * a + j], hh, mm, ll);
         unsigned char* d = lds + SC_OFF + kcw * KSC + i * 32 + (((kqw >> 1) ^ ((i >> 3) & 1)) << 4) + (kqw & 1) * 8;
         *reinterpret_cast<u32x2*>(d) = hh;
         *reinterpret_cast<u32x2*>(d + PLSC) = mm;
@@ -535,7 +514,7 @@ __global__ __launch_bounds__(kThreads, 3) void bottleneck_tail_planes_kernel(typ
       for (int ps = 0; ps < 8; ++ps) {
         const int i = (lane >> 5) * 32 + er0 + ps * 4;
         u32x2 hh, mm, ll;
-        split3p(vs[c][ps], hh, mm, ll);
+        split3(vs[c][ps], hh, mm, ll);
         unsigned char* d = lds + kcl * KSN + i * 32 + (((kqn >> 1) ^ ((i >> 3) & 1)) << 4) + (kqn & 1) * 8;
         *reinterpret_cast<u32x2*>(d) = hh;
         *reinterpret_cast<u32x2*>(d + PLN) = mm;

@@ -29,40 +29,12 @@
 //     an LDS transpose: 16-byte residual loads and stores.
 #include <stdlib.h>
 
-#include "conv_args.h"
+#include "bfx_internal.h"
 #include "bfx_split.h"
 
 using namespace bgs_conv;
 
 namespace {
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-  const bf16x2 h = __builtin_convertvector(f32x2{a, b}, bf16x2);   // v_cvt_pk_bf16_f32 (RNE)
-  return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) {
-  return __builtin_bit_cast(float, u & 0xffff0000u);
-}
-// x (4 consecutive k) -> three planes of 4 packed bf16 each (conv_bfx.hip's split3)
-__device__ __forceinline__ void split3(const f32x4 v, u32x2& hi, u32x2& mid, u32x2& lo) {
-  hi = u32x2{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
-  const f32x4 r = {bfx_resid_lo(hi[0], v[0]), bfx_resid_hi(hi[0], v[1]), bfx_resid_lo(hi[1], v[2]),
-                   bfx_resid_hi(hi[1], v[3])};
-  mid = u32x2{pack_bf16(r[0], r[1]), pack_bf16(r[2], r[3])};
-  const f32x4 r2 = {bfx_resid_lo(mid[0], r[0]), bfx_resid_hi(mid[0], r[1]), bfx_resid_lo(mid[1], r[2]),
-                    bfx_resid_hi(mid[1], r[3])};
-  lo = u32x2{pack_bf16(r2[0], r2[1]), pack_bf16(r2[2], r2[3])};
-}
-__device__ __forceinline__ void glds16(const void* src, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 struct BresArgs {
   const unsigned* zero;  // device zero page: DMA source of rows past M

@@ -1,12 +1,12 @@
 // 1x1 convolution / linear layer on the bf16 matrix cores with the A-operand split taken OUT of the MFMA loop
 // (round 6).  Same contract and arithmetic as the 1x1 instantiations of conv_bfx.hip
 // (mmdet/models/backbones/resnet.py:220-266 conv1 / conv3 / downsample, necks/fpn.py:118-127 lateral convs): fp32 NHWC in,
-// fp32 out, every product from the exact three-way bf16 split of both operands, fp32 accumulate, bias / residual / ReLU.
+// fp32 out, every product from the exact three-way bf16 split of both operands, fp32 accumulate, bias / residual / ReLU / ReLU-backward mask.
 //
 // What the existing kernels do: the 64 x 64 operand ring and the 128 x 128 wide kernel deliver A as fp32 and split it in
 // registers when a wave reads its fragment — 44 VALU instructions beside 6 (ring) or 24 (wide) MFMAs, repeated by every
 // workgroup that covers the same pixels for another slice of the output channels (2 - 16 of them), and VALU and MFMA time
-// add on a SIMD (profiles/r9c).  Here a workgroup owns 64 pixels x 256 output channels:
+// add on a SIMD (profiles/r9c).  Here a workgroup owns 64 pixels x 256 (or 128) output channels:
 //   * per 64-deep K chunk the [64 pixels x 64 k] fp32 tile is loaded ONCE (16-byte buffer loads, the next chunk in flight
 //     under this chunk's MFMAs), split ONCE (4 split3 per thread) and written to LDS as three bf16 planes in the B
 //     layout ([plane][k step][pixel][32 B], halves swapped on odd 8-pixel groups: conflict-free ds_read_b128), double
@@ -22,33 +22,12 @@
 // tensors below 2 GB (32-bit buffer offsets).
 #include <stdlib.h>
 
-#include "conv_args.h"
+#include "bfx_internal.h"
 #include "bfx_split.h"
 
 using namespace bgs_conv;
 
 namespace {
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-  const bf16x2 h = __builtin_convertvector(f32x2{a, b}, bf16x2);   // v_cvt_pk_bf16_f32 (RNE)
-  return __builtin_bit_cast(unsigned, h);
-}
-
-// x (4 consecutive k) -> three planes of 4 packed bf16 each: conv_bfx.hip's split3, verbatim
-__device__ __forceinline__ void split3p(const f32x4 v, u32x2& hi, u32x2& mid, u32x2& lo) {
-  hi = u32x2{pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3])};
-  const f32x4 r = {bfx_resid_lo(hi[0], v[0]), bfx_resid_hi(hi[0], v[1]), bfx_resid_lo(hi[1], v[2]),
-                   bfx_resid_hi(hi[1], v[3])};
-  mid = u32x2{pk_bf16(r[0], r[1]), pk_bf16(r[2], r[3])};
-  const f32x4 r2 = {bfx_resid_lo(mid[0], r[0]), bfx_resid_hi(mid[0], r[1]), bfx_resid_lo(mid[1], r[2]),
-                    bfx_resid_hi(mid[1], r[3])};
-  lo = u32x2{pk_bf16(r2[0], r2[1]), pk_bf16(r2[2], r2[3])};
-}
 
 struct PlanesArgs {
   ConvArgs c;
@@ -112,7 +91,7 @@ __global__ __launch_bounds__(kThreads, 3) void conv1x1_planes_bfx_kernel(PlanesA
     for (int ps = 0; ps < 4; ++ps) {
       const int i = r0 + 16 * ps;
       u32x2 hh, mm, ll;
-      split3p(ra[ps], hh, mm, ll);
+      split3(ra[ps], hh, mm, ll);
       unsigned char* d = lds + buf * BUF + kcs_w * CH + i * 32 + (((kq_w >> 1) ^ ((i >> 3) & 1)) << 4) + (kq_w & 1) * 8;
       *reinterpret_cast<u32x2*>(d) = hh;
       *reinterpret_cast<u32x2*>(d + PL) = mm;

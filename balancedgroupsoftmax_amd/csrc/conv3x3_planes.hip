@@ -41,33 +41,12 @@
 #ifndef BGS_P3_ABL
 #define BGS_P3_ABL 0             // timing-only ablations (build variants p3abl1 / p3abl2 / p3abl3; results are WRONG)
 #endif
-#include "conv_args.h"
+#include "bfx_internal.h"
 #include "bfx_split.h"
 
 using namespace bgs_conv;
 
 namespace {
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-  const bf16x2 h = __builtin_convertvector(f32x2{a, b}, bf16x2);   // v_cvt_pk_bf16_f32 (RNE)
-  return __builtin_bit_cast(unsigned, h);
-}
-
-// x (4 consecutive k) -> three planes of 4 packed bf16 each: conv_bfx.hip's split3, verbatim
-__device__ __forceinline__ void split3p(const f32x4 v, u32x2& hi, u32x2& mid, u32x2& lo) {
-  hi = u32x2{pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3])};
-  const f32x4 r = {bfx_resid_lo(hi[0], v[0]), bfx_resid_hi(hi[0], v[1]), bfx_resid_lo(hi[1], v[2]),
-                   bfx_resid_hi(hi[1], v[3])};
-  mid = u32x2{pk_bf16(r[0], r[1]), pk_bf16(r[2], r[3])};
-  const f32x4 r2 = {bfx_resid_lo(mid[0], r[0]), bfx_resid_hi(mid[0], r[1]), bfx_resid_lo(mid[1], r[2]),
-                    bfx_resid_hi(mid[1], r[3])};
-  lo = u32x2{pk_bf16(r2[0], r2[1]), pk_bf16(r2[2], r2[3])};
-}
 
 struct Planes3Args {
   ConvArgs c;
@@ -149,7 +128,7 @@ __global__ __launch_bounds__(kThreads, 3) void conv3x3_planes_bfx_kernel(typenam
     for (int i = 0; i < 4; ++i) {
       if (a_dst[i] < 0) continue;
       u32x2 hh, mm, ll;
-      split3p(ra[i], hh, mm, ll);
+      split3(ra[i], hh, mm, ll);
       unsigned char* d = lds + buf * BUF + a_dst[i];
       *reinterpret_cast<u32x2*>(d) = hh;
       *reinterpret_cast<u32x2*>(d + PL) = mm;
@@ -323,8 +302,8 @@ __global__ __launch_bounds__(kThreads, 3) void conv3x3_planes_bfx_kernel(typenam
         const f32x4 v0 = *reinterpret_cast<const f32x4*>(srow + u * 16);
         const f32x4 v1 = *reinterpret_cast<const f32x4*>(srow + u * 16 + 4);
         u32x2 h0, m0, l0, h1, m1, l1;
-        split3p(v0, h0, m0, l0);
-        split3p(v1, h1, m1, l1);
+        split3(v0, h0, m0, l0);
+        split3(v1, h1, m1, l1);
         bf16x8 fa[NS];
         fa[0] = __builtin_bit_cast(bf16x8, u32x4{h0[0], h0[1], h1[0], h1[1]});
         fa[1] = __builtin_bit_cast(bf16x8, u32x4{m0[0], m0[1], m1[0], m1[1]});
@@ -469,7 +448,7 @@ __global__ __launch_bounds__(kThreads, 3) void conv3x3s2_planes_bfx_kernel(Plane
     for (int i = 0; i < AQT; ++i) {
       if (a_dst[i] < 0) continue;
       u32x2 hh, mm, ll;
-      split3p(ra[i], hh, mm, ll);
+      split3(ra[i], hh, mm, ll);
       unsigned char* d = lds + a_dst[i];
       *reinterpret_cast<u32x2*>(d) = hh;
       *reinterpret_cast<u32x2*>(d + PL) = mm;
@@ -655,9 +634,6 @@ int bgs_internal_conv3x3_planes(const bgs_conv::ConvArgs& pc, const void* wsplit
 }
 
 // ---- rpn_conv + the 1x1 RPN heads in one launch (the HEAD form of conv3x3_planes_bfx_kernel<2>)
-int bgs_internal_halo_hooks_default();                                   // conv_bfx.hip: no forced slice count / variant / pixel tile
-int bgs_internal_bfx_unsliced(long long M, int Cout, int KC);           // conv_bfx.hip: the operand ring would run this layer with ONE K slice
-
 // 1 when the default dispatch puts the 3x3 conv of this map on the 256-channel planes kernel AND would run the 1x1 head
 // [Chead][Cout] on it with one K slice (the arithmetic the fused epilogue reproduces bit for bit); pure host logic
 extern "C" int bgs_conv3x3_planes_head_eligible(int N, int H, int W, int Cin, int Cout, int Chead) {

@@ -1,5 +1,5 @@
-// Shared by the implicit-GEMM convolution kernels (conv_igemm.hip: fp32 MFMA; conv_bfx.hip: bf16
-// MFMA on split operands): the argument block and the fused epilogue.
+// Shared by the implicit-GEMM convolution kernels (conv_igemm.hip: fp32 MFMA; conv_bfx.hip and the
+// other bf16x6 files, bfx_internal.h: bf16 MFMA on split operands): the argument block and the fused epilogue.
 #pragma once
 
 #include "bgs_common.h"

@@ -30,15 +30,11 @@
 #include <stdlib.h>
 
 #include "conv_args.h"
+#include "bfx_split.h"
 
 using namespace bgs_conv;
 
 namespace {
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __attribute__((aligned(16))) unsigned g_bf16s_zero_page[16];
 
@@ -59,20 +55,6 @@ struct Bf16sArgs {
   // the whole filter exceed the 4 MB of the XCD's L2.  sb == 0: row-tile-major (column tiles fastest).
   int mpx, sb;
 };
-
-__device__ __forceinline__ void glds16(const void* src, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-  const bf16x2 h = __builtin_convertvector(f32x2{a, b}, bf16x2);   // v_cvt_pk_bf16_f32 (RNE)
-  return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) {
-  return __builtin_bit_cast(float, u & 0xffff0000u);
-}
 
 // Epilogue of a 128 x 128 tile held by eight waves (4 x 2, each 32 x 64 as two 32 x 32 accumulators):
 // LDS transpose in two halves of 64 rows (scratch 64 x 132 floats at the start of `lds`, which no wave reads
@@ -588,7 +570,7 @@ extern "C" int bgs_conv2d_nhwc_bf16s(const void* x, const void* w_hi, const floa
   if (M > 0x7fffffffLL) return BGS_ERR_UNSUPPORTED;
   p.M = (int)M;
   p.K = R * S * Cin;
-  p.KC = 2 * ((p.K + 31) / 32);
+  p.KC = bfx_kc(p.K);
   p.relu = relu;
   p.res_mode = residual_mode;
   p.res_bf16 = residual_bf16;

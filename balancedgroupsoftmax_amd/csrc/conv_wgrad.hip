@@ -26,8 +26,6 @@
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kThreads = 256;
@@ -246,28 +244,8 @@ __global__ __launch_bounds__(kThreads) void conv_wgrad_f32_kernel(WgradArgs p) {
 // ds_read_tr / ds_bpermute.  Threads 0-127 stage dy (and accumulate the bias gradient), 128-255 the
 // im2col rows of x.  128 x 128 tile, 2 x 2 waves, 24 MFMAs per wave and stage, LDS double-buffered
 // (72 KB: two workgroups per CU); reduction split over gridDim.z and summed in a fixed order as above.
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __attribute__((aligned(16))) float g_wgrad_zero[4];
-
-__device__ __forceinline__ unsigned wg_pack_bf16(float a, float b) {
-  const bf16x2 h = __builtin_convertvector(f32x2{a, b}, bf16x2);   // v_cvt_pk_bf16_f32 (RNE)
-  return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float wg_bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float wg_bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-__device__ __forceinline__ void wg_split3(const f32x4 v, u32x2& hi, u32x2& mid, u32x2& lo) {
-  hi = u32x2{wg_pack_bf16(v[0], v[1]), wg_pack_bf16(v[2], v[3])};
-  const f32x4 r = {bfx_resid_lo(hi[0], v[0]), bfx_resid_hi(hi[0], v[1]), bfx_resid_lo(hi[1], v[2]),
-                   bfx_resid_hi(hi[1], v[3])};
-  mid = u32x2{wg_pack_bf16(r[0], r[1]), wg_pack_bf16(r[2], r[3])};
-  const f32x4 r2 = {bfx_resid_lo(mid[0], r[0]), bfx_resid_hi(mid[0], r[1]), bfx_resid_lo(mid[1], r[2]),
-                    bfx_resid_hi(mid[1], r[3])};
-  lo = u32x2{wg_pack_bf16(r2[0], r2[1]), wg_pack_bf16(r2[2], r2[3])};
-}
 
 // NS = 3: fp32-faithful; NS = 1: operands rounded to bf16 (the bf16 mode of cfg[4])
 // ABL (only instantiated != 0 under -DBGS_ABLATE, tools/wgrad_ablate.py): timing-only variants that drop one
@@ -369,7 +347,7 @@ __global__ __launch_bounds__(kThreads, NBUF == 1 ? 3 : 2) void conv_wgrad_bfx_ke
         m = u32x2{__float_as_uint(v[2][j]), __float_as_uint(v[3][j])};
         l = h;
       } else {
-        wg_split3(f32x4{v[0][j], v[1][j], v[2][j], v[3][j]}, h, m, l);
+        split3(f32x4{v[0][j], v[1][j], v[2][j], v[3][j]}, h, m, l);
       }
       *reinterpret_cast<u32x2*>(base + j * LDR) = h;
       if (NS >= 2) *reinterpret_cast<u32x2*>(base + j * LDR + PLANE) = m;

@@ -34,13 +34,7 @@
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
 constexpr int kCout = 64;
@@ -55,22 +49,6 @@ constexpr int PATCH_BYTES = 3 * PLANE_BYTES;                                    
 constexpr int OUT_LD = 32 + 4;              // conv tile in LDS, one 32-channel half at a time: [363][36] fp32 = 52,272 bytes
 constexpr int OUT_BYTES = CT_PX * OUT_LD * 4;
 constexpr int LDS_BYTES = OUT_BYTES > PATCH_BYTES ? OUT_BYTES : PATCH_BYTES;
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-  const bf16x2 h = __builtin_convertvector(f32x2{a, b}, bf16x2);   // v_cvt_pk_bf16_f32 (RNE)
-  return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-
-// x (4 consecutive k) -> three planes of 4 packed bf16 each (the split of csrc/conv_bfx.hip)
-__device__ __forceinline__ void split3(const f32x4 v, u32x2& hi, u32x2& mid, u32x2& lo) {
-  hi = u32x2{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
-  const f32x4 r = {bfx_resid_lo(hi[0], v[0]), bfx_resid_hi(hi[0], v[1]), bfx_resid_lo(hi[1], v[2]), bfx_resid_hi(hi[1], v[3])};
-  mid = u32x2{pack_bf16(r[0], r[1]), pack_bf16(r[2], r[3])};
-  const f32x4 r2 = {bfx_resid_lo(mid[0], r[0]), bfx_resid_hi(mid[0], r[1]), bfx_resid_lo(mid[1], r[2]), bfx_resid_hi(mid[1], r[3])};
-  lo = u32x2{pack_bf16(r2[0], r2[1]), pack_bf16(r2[2], r2[3])};
-}
 
 // w [64][7][7][cin_stride] fp32 (folded, channels 0..2 used) -> out [3 planes][28 blocks][64 cout][8] bf16:
 // block = 4 ky + g, element j of it = filter column kx = 2 g + j / 4, channel c = j % 4 (kx = 7 and c = 3: zeros)

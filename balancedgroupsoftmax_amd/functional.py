@@ -1130,7 +1130,7 @@ def fused_c3_eligible(x, w2, w3, stride, residual):
             and tuple(w2.shape[:3]) == (64, 3, 3) and w2.shape[3] == 64 and tuple(w3.shape) == (256, 1, 1, 64)
             and x.shape[3] == 64 and _use_halo_bfx(x.shape[0] * x.shape[1] * x.shape[2], 64)
             # (>= 700 pixel tiles: below that the unfused conv2 splits its channel chunks over gridDim.z — another
-            #  summation order — and a short grid gains nothing from the fusion; csrc/conv_bfx.hip halo_bfx_plan)
+            #  summation order — and a short grid gains nothing from the fusion; csrc/conv3x3_halo_bfx.hip halo_bfx_plan)
             and x.shape[0] * ((x.shape[1] + 7) // 8) * ((x.shape[2] + 15) // 16) >= 700
             and not (torch.is_grad_enabled() and (x.requires_grad or w2.requires_grad or w3.requires_grad or
                                                   (residual is not None and residual.requires_grad)))

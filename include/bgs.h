@@ -309,7 +309,8 @@ int bgs_conv3x3_halo_nhwc_f32(const float* x, const float* w, const float* bias,
 
 /* ------------------------------------------------------------------------------------
  * The same convolutions on the bf16 matrix cores with fp32-faithful results ("bf16x6",
- * csrc/conv_bfx.hip): every fp32 operand is split exactly into three bf16 terms
+ * csrc/conv_bfx.hip; the 3x3 halo kernels: conv3x3_halo_bfx.hip, the filter split:
+ * bfx_weights.hip): every fp32 operand is split exactly into three bf16 terms
  * (hi + mid + lo, round-to-nearest-even) and the six products with i + j <= 2 are accumulated
  * in fp32 by v_mfma_f32_32x32x16_bf16 — 6/16 of the matrix-pipe time of the fp32 MFMA kernel at
  * the same error against an fp64 reference (dropped terms <= 2^-25 |a b|).  Same call sites and

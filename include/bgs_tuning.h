@@ -78,7 +78,7 @@ int bgs_gs_head_variant_used(int N);
  *   register-staged 64 x 64 kernel instead of the LDS-DMA ring; + 0x400 / 0x800: force the 3- / 4-stage ring),
  *   splitk -1 = auto | 1..16; bgs_conv_bfx_last_launch: *tile carries the tile | 0x200 (DMA ring) | 0x400
  *   (3 stages) | 0x1000 (filter-resident 1x1) | 0x2000 (parity-class data gradient) | 0x4000 (wide 1x1).
- * bgs_conv3x3_halo_bfx_tuning: splits -1 = auto | n; variant 0 = default = 4 (filter slices by LDS-DMA) | 2
+ * bgs_conv3x3_halo_bfx_tuning (csrc/conv3x3_halo_bfx.hip): splits -1 = auto | n; variant 0 = default = 4 (filter slices by LDS-DMA) | 2
  *   (register-staged slices; every other value selects 4); bits 16..19 of `variant`: the pixel
  *   tile of variant 4, 0 = default (8 x 16; env BGS_HALO_GEOM) | 1 = 8 x 16 | 2 = 10 x 12 | 3 = 5 x 21 | 4 = the
  *   tile with the fewest tiles per image;

@@ -810,7 +810,7 @@ def test_halo_wide_pixel_tile_is_bit_identical_to_variant_4(case, monkeypatch):
                                    (1, 25, 42, 256, 200, True), (2, 50, 84, 32, 64, False),
                                    (1, 3, 5, 48, 15, True), (1, 200, 513, 16, 128, True)])
 def test_conv3x3_halo_kernel_vs_torch_cpu(monkeypatch, shape, conv_math):
-    """csrc/conv_halo.hip / the halo kernel of csrc/conv_bfx.hip (input patch + halo staged in LDS
+    """csrc/conv_halo.hip / the halo kernel of csrc/conv3x3_halo_bfx.hip (input patch + halo staged in LDS
     once per channel chunk, shared by the nine taps) == torch-CPU F.conv2d and == the general
     implicit-GEMM kernel: tiles that hang over the image, Cout that is not a multiple of the
     128-wide tile, one pixel tile only, and a shape large enough for the DEFAULT dispatch to

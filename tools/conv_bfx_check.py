@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""bf16x6 convolution kernels (csrc/conv_bfx.hip) on the GPU box:
+"""bf16x6 convolution kernels (csrc/conv_bfx.hip, conv3x3_halo_bfx.hip) on the GPU box:
 
   1. error of the fp32 MFMA kernel and of the bf16x6 kernels against an fp64 torch-CPU reference on
      a set of shapes that covers every epilogue / tile / stride / dgrad mode;
