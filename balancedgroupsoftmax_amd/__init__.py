@@ -4,7 +4,7 @@ Hand-written gfx950 HIP kernels behind a C ABI (``include/bgs.h`` -> ``libbgs.so
 from PyTorch-ROCm through the reference's own registry keys and config schema.
 """
 from . import (backbone, bbox_heads, checkpoint, config, detectors, gs_tables, losses, lvis_eval,  # noqa: F401
-               mask_heads, roi_extractor, rpn, semantic_head, tnorm, train)  # (imports populate the registries)
+               mask_heads, recall, roi_extractor, rpn, semantic_head, tnorm, train)  # (imports populate the registries)
 from .apis import inference_detector, init_detector
 from .builder import (build_backbone, build_detector, build_head, build_loss, build_neck,
                       build_roi_extractor, build_shared_head)
@@ -16,6 +16,8 @@ from .lvis_eval import LVISEval, LVISGroundTruth, ResultArrays, results2arrays, 
 from .ops import (DeformConv, DeformConvPack, ModulatedDeformConv, ModulatedDeformConvPack, deform_conv,
                   modulated_deform_conv)
 from .post_processing import packed2arrays
+from .recall import (eval_recalls, lvis_fast_eval_recall, lvis_fast_eval_recall_percat, print_recall_summary,
+                     proposal2json)
 from .pipelines import TestPipeline, TrainPipeline, rescale_size
 from .tnorm import ProposalAccuracy, reweight_cls_newhead, tail_mask
 from .registry import (BACKBONES, DETECTORS, HEADS, LOSSES, NECKS, ROI_EXTRACTORS, SHARED_HEADS,
@@ -31,4 +33,5 @@ __all__ = ['BACKBONES', 'DETECTORS', 'HEADS', 'LOSSES', 'NECKS', 'ROI_EXTRACTORS
            'DeformConv', 'DeformConvPack', 'ModulatedDeformConv', 'ModulatedDeformConvPack', 'deform_conv',
            'modulated_deform_conv', 'FocalLoss', 'ReweightBBoxHead', 'sigmoid_focal_loss',
            'sigmoid_focal_loss_elementwise', 'tnorm', 'ProposalAccuracy', 'reweight_cls_newhead', 'tail_mask',
-           'ResultArrays', 'results2arrays', 'packed2arrays']
+           'ResultArrays', 'results2arrays', 'packed2arrays', 'recall', 'eval_recalls', 'lvis_fast_eval_recall',
+           'lvis_fast_eval_recall_percat', 'print_recall_summary', 'proposal2json']

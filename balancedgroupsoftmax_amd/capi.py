@@ -224,6 +224,10 @@ SIGNATURES = {
                        + [c_ptr, ctypes.c_int, c_ptr, ctypes.c_int, c_ptr, ctypes.c_size_t] + [c_ptr] * 4 + [c_ptr]),
     'bgs_lvis_accumulate': (ctypes.c_int, [c_ptr] * 5 + [ctypes.c_int] + [ctypes.c_longlong] * 2
                             + [ctypes.c_int, ctypes.c_int, c_ptr, ctypes.c_int, c_ptr, c_ptr, c_ptr]),
+    'bgs_recall_match_lds_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    'bgs_recall_match': (ctypes.c_int, [c_ptr] * 5 + [c_ptr, ctypes.c_int, c_ptr, ctypes.c_int]
+                         + [ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int,
+                            ctypes.c_int, c_ptr, c_ptr, c_ptr]),
     'bgs_poly_rle_edge_points': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.c_longlong, ctypes.c_int, c_ptr, c_ptr]),
     'bgs_poly_rle_crossings': (ctypes.c_int, [c_ptr] * 4 + [ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_ptr, c_ptr,
                                               ctypes.c_longlong, c_ptr, c_ptr, c_ptr]),

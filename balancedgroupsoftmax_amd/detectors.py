@@ -379,6 +379,23 @@ class TwoStageDetector(nn.Module):
         cls_scores, bbox_preds = self.rpn_head(x)
         return self.rpn_head.get_bboxes(cls_scores, bbox_preds, img_meta, rpn_test_cfg)
 
+    def simple_test_proposals(self, img, img_meta, rescale=False):
+        """What the reference's RPN detector tests with (detectors/rpn.py:62-69, the run behind ``--eval
+        proposal_fast``): ``extract_feat`` -> ``simple_test_rpn``; with ``rescale`` every image's boxes are divided by
+        its ``scale_factor`` (``proposals[:, :4] /= meta['scale_factor']``).  Returns the device pair ``(props
+        [B, max_num, 5], valid [B, max_num])``, what :func:`recall.eval_recalls` takes as it is; nothing is read
+        back."""
+        self._refuse_test_mode()
+        with torch.no_grad():
+            x = self.extract_feat(img)
+            props, valid = self.simple_test_rpn(x, img_meta, self.test_cfg.rpn).batched
+            if rescale:
+                props = props.clone()
+                for b, meta in enumerate(img_meta):
+                    sf = meta['scale_factor']
+                    props[b, :, :4] /= sf if isinstance(sf, float) else torch.as_tensor(sf).to(props.device)
+        return props, valid
+
     def simple_test_bboxes(self, x, img_meta, proposals, rcnn_test_cfg, rescale=False, ctx=None):
         """test_mixins.py:39-67 for ONE image (the reference tests with imgs_per_gpu=1): RoIAlign -> head -> merged
         scores + decoded boxes -> one batched 1230-class NMS.  The cascades (cascade_rcnn.py:300-393,

@@ -3404,6 +3404,115 @@ def lvis_accumulate(dt_bits, gt_ignore, dt_score, cat_dt_off, cat_gt_off, rec_th
     return precision, recall
 
 
+# ----------------------------------------------------------------------------------------
+# Proposal recall  (mmdet/core/evaluation/recall.py:7-37, bbox_overlaps.py:4-49; csrc/recall_match.hip)
+# ----------------------------------------------------------------------------------------
+RECALL_MAX_K, RECALL_MAX_T = 8, 16
+RECALL_MAX_G, RECALL_MAX_N = 2048, 4096
+
+
+def _recall_boxes(t, what):
+    if t.dim() != 2 or t.shape[1] != 4:
+        raise ValueError('recall_match: %s must be [n, 4] (x1, y1, x2, y2), got %r' % (what, tuple(t.shape)))
+    t = t.detach().to(torch.float32).contiguous()
+    return t.clone() if t.data_ptr() % 16 else t       # (the kernel loads a box as one 16-byte word)
+
+
+def _recall_check_boxes(b, what):
+    """finite, x2 - x1 + 1 > 0 and a finite positive float32 area, on the device: one host read"""
+    if b.shape[0]:
+        w, h = b[:, 2] - b[:, 0] + 1, b[:, 3] - b[:, 1] + 1
+        area = w * h
+        if not bool((torch.isfinite(b).all(dim=1) & torch.isfinite(area) & (area > 0) & (w > 0)).all()):
+            raise ValueError('recall_match: %s must be finite boxes of positive area' % what)
+
+
+def _recall_table(a, dtype, what):
+    import numpy as np
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise ValueError('recall_match: %s must be a 1-d integer table' % what)
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def recall_match(gt_boxes, gt_off, prob_img, prop_boxes, prop_off, proposal_nums, iou_thrs, check=True):
+    """``bbox_overlaps`` + the greedy assignment of ``_recalls`` (recall.py:16-29) + its threshold counts (recall.py:35)
+    for every problem and every proposal count in one launch (``bgs_recall_match``).
+
+    ``gt_boxes [NG, 4]`` / ``prop_boxes [NP, 4]``: float32 device tensors ``(x1, y1, x2, y2)``, the proposals already
+    in evaluation order inside each image.  ``gt_off [P + 1]``, ``prob_img [P]``, ``prop_off [n_img + 1]``: integer
+    tables (numpy arrays or lists; a tensor is copied to the host, they are validated there): problem ``p`` owns ground
+    truths ``gt_off[p]:gt_off[p + 1]`` and reads the proposals ``prop_off[i]:prop_off[i + 1]`` of image ``i =
+    prob_img[p]``.  ``proposal_nums [K]`` ascending ints (K <= 8), ``iou_thrs [T]`` float64 values (T <= 16).
+    At most 2048 ground truths per problem and ``min(proposals of an image, proposal_nums[-1]) <= 4096``.
+    Boxes must be finite with positive area (``ValueError``): the reference divides by zero or carries NaN there;
+    ``check=False`` is for a caller that has made that check itself (``recall.py`` on its host arrays).  A box is loaded
+    as one 16-byte word: a tensor whose data does not begin on a 16-byte boundary is copied first.
+
+    Returns device tensors ``(gt_ious float32 [K, NG], counts int32 [P, K, T])``: ``gt_ious[k, gt_off[p] + j]`` is the
+    IoU of the j-th pick of problem ``p`` (-1 once the proposals ran out, 0 with no proposal at all),
+    ``counts[p, k, t]`` the number of its picks with ``float64(iou) >= iou_thrs[t]``."""
+    import numpy as np
+    gt = _recall_boxes(gt_boxes, 'gt_boxes')
+    pr = _recall_boxes(prop_boxes, 'prop_boxes')
+    if pr.device != gt.device:
+        raise ValueError('recall_match: gt_boxes and prop_boxes must be on one device')
+    gt_off = _recall_table(gt_off, np.int64, 'gt_off')
+    prob_img = _recall_table(prob_img, np.int32, 'prob_img')
+    prop_off = _recall_table(prop_off, np.int64, 'prop_off')
+    nums = np.asarray(proposal_nums)
+    if nums.ndim != 1 or nums.size < 1 or not np.issubdtype(nums.dtype, np.integer):
+        raise ValueError('recall_match: proposal_nums must be a non-empty 1-d integer array')
+    thr = np.ascontiguousarray(iou_thrs, dtype=np.float64).reshape(-1)
+    K, T = int(nums.size), int(thr.size)
+    if K > RECALL_MAX_K:
+        raise ValueError('recall_match: at most %d proposal_nums, got %d' % (RECALL_MAX_K, K))
+    if T < 1 or T > RECALL_MAX_T:
+        raise ValueError('recall_match: between 1 and %d iou_thrs, got %d' % (RECALL_MAX_T, T))
+    if (nums < 0).any() or (np.diff(nums) < 0).any() or nums.max() > 0x7fffffff:
+        raise ValueError('recall_match: proposal_nums must be non-negative and ascending, got %r' % (nums.tolist(),))
+    nums = np.ascontiguousarray(nums, dtype=np.int32)
+    NG, NP = int(gt.shape[0]), int(pr.shape[0])
+    for o, n, what in ((gt_off, NG, 'gt_off'), (prop_off, NP, 'prop_off')):
+        if o.size < 1 or o[0] != 0 or (np.diff(o) < 0).any() or o[-1] != n:
+            raise ValueError('recall_match: %s must start at 0, never decrease and end at %d' % (what, n))
+    P, n_img = int(gt_off.size) - 1, int(prop_off.size) - 1
+    if prob_img.size != P:
+        raise ValueError('recall_match: prob_img must be [P] = [%d], got %r' % (P, prob_img.shape))
+    if P and (prob_img.min() < 0 or prob_img.max() >= n_img):
+        raise ValueError('recall_match: prob_img must lie in [0, %d)' % n_img)
+    max_g = int(np.diff(gt_off).max()) if P else 0
+    max_n = int(min(np.diff(prop_off)[prob_img].max(), nums[-1])) if P else 0
+    if max_g > RECALL_MAX_G:
+        raise ValueError('recall_match: a problem holds %d ground truths, the limit is %d' % (max_g, RECALL_MAX_G))
+    if max_n > RECALL_MAX_N:
+        raise ValueError('recall_match: %d proposals of one image are in use, the limit is %d (lower proposal_nums)'
+                         % (max_n, RECALL_MAX_N))
+    _require_cuda(gt, pr)                  # (the tables above are host work: their refusals need no device)
+    dev = gt.device
+    with torch.cuda.device(dev):
+        if check:
+            _recall_check_boxes(gt, 'gt_boxes')
+            _recall_check_boxes(pr, 'prop_boxes')
+        gt_ious = torch.zeros((K, NG), dtype=torch.float32, device=dev)
+        counts = torch.zeros((P, K, T), dtype=torch.int32, device=dev)
+        if P == 0:
+            return gt_ious, counts
+        # one upload: the int64 offsets and (as int64) the image of each problem
+        table = torch.from_numpy(np.concatenate([gt_off, prop_off, prob_img.astype(np.int64)])).to(dev)
+        gt_off_d, prop_off_d = table[:P + 1], table[P + 1:P + n_img + 2]
+        prob_img_d = table[P + n_img + 2:].to(torch.int32)
+        lib = capi.load()
+        rc = lib.bgs_recall_match(capi.ptr(gt), capi.ptr(gt_off_d), capi.ptr(prob_img_d), capi.ptr(pr),
+                                  capi.ptr(prop_off_d), nums.ctypes.data_as(ctypes.c_void_p), K,
+                                  thr.ctypes.data_as(ctypes.c_void_p), T, P, n_img, NG, NP, max_g, max_n,
+                                  capi.ptr(gt_ious), capi.ptr(counts), capi.current_stream(dev))
+    capi.check('bgs_recall_match', rc)
+    return gt_ious, counts
+
+
 def mask_gt_logits(feat, weight, bias, labels):
     """``feat [P, pixels, C]``, ``weight [K, C]``, ``labels [P]`` -> ``[P, pixels]`` logits of each
     RoI's own class channel (no gradient: test-time / inspection path)."""

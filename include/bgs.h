@@ -1102,6 +1102,37 @@ int bgs_lvis_accumulate(const unsigned* dt_bits, const uint8_t* gt_ignore, const
                         int A, int T, const double* host_rec_thrs, int R, double* precision, double* recall,
                         bgs_stream_t stream);
 
+/* Proposal recall (csrc/recall_match.hip): what tools/test_lvis.py --eval proposal_fast[_percat] reaches through
+ * lvis_fast_eval_recall -> eval_recalls: bbox_overlaps (mmdet/core/evaluation/bbox_overlaps.py:4-49) and the greedy
+ * assignment and threshold counts of _recalls (mmdet/core/evaluation/recall.py:7-37), for every PROBLEM and every
+ * proposal count in one launch.  Problem p owns ground truths gt_off[p] .. gt_off[p + 1] of gt_boxes [NG, 4] float
+ * (x1, y1, x2, y2) and reads the proposals of image prob_img[p]: rows prop_off[i] .. prop_off[i + 1] of prop_boxes
+ * [NP, 4] float, already in evaluation order (descending score); several problems may name the same image (one per
+ * category in the per-category evaluation).  gt_off [P + 1] / prop_off [n_img + 1] device int64, non-decreasing,
+ * prob_img [P] device int32.  host_proposal_nums [K] int32 (HOST, ascending, >= 0: BGS_ERR_INVALID_ARG otherwise) and
+ * host_iou_thrs [T] fp64 (HOST); K <= 8 and T <= 16.  max_g / max_n: the caller's bounds on the ground truths of one
+ * problem and on min(proposals of one image, host_proposal_nums[K - 1]); max_g <= 2048 and max_n <= 4096
+ * (BGS_ERR_UNSUPPORTED beyond, before any launch); they size the LDS, bgs_recall_match_lds_bytes(max_g, max_n) =
+ * 28 * max_g + 16 * max_n + 4 * ceil(max_n / 32) bytes.  A problem that exceeds them, or whose offsets leave
+ * [0, NG] / [0, NP] or whose image is outside [0, n_img), counts 0 and writes no IoU.
+ *   For (p, k), N = min(proposals of the image, host_proposal_nums[k]) and G = the problem's ground truths:
+ *   iou(g, c) = ov / ((area_g + area_c) - ov), area = (x2 - x1 + 1) * (y2 - y1 + 1),
+ *   ov = max(xe - xs + 1, 0) * max(ye - ys + 1, 0): float32, one correctly rounded operation at a time (no fused
+ *   multiply-add), the bits numpy gives.  For j = 0 .. G - 1: among the live rows and columns take the maximum IoU,
+ *   the lowest ground truth and then the lowest proposal among equals (numpy's first-index argmax over a matrix whose
+ *   removed entries are -1), write it to gt_ious[k, gt_off[p] + j] (the j-th PICK, not ground truth j's), remove its
+ *   row and column; once no column is left every further j gets -1; N == 0 gives 0 everywhere (recall.py:19-21).
+ *   counts[p, k, t] = the number of j with (double)gt_ious >= host_iou_thrs[t] (recall.py:35).
+ *   Boxes must be finite with area > 0 (the caller checks; a NaN IoU is never picked here).  gt_boxes and prop_boxes
+ *   must be 16-byte aligned: a box is loaded as one 16-byte word (BGS_ERR_INVALID_ARG otherwise).
+ * Outputs: gt_ious [K, NG] float (entries no problem owns are left alone), counts [P, K, T] int32, every element
+ * written.  No atomics: two calls return the same bits.  P == 0 is BGS_OK. */
+size_t bgs_recall_match_lds_bytes(int max_g, int max_n);
+int bgs_recall_match(const float* gt_boxes, const long long* gt_off, const int* prob_img, const float* prop_boxes,
+                     const long long* prop_off, const int* host_proposal_nums, int K, const double* host_iou_thrs,
+                     int T, int P, int n_img, long long NG, long long NP, int max_g, int max_n, float* gt_ious,
+                     int* counts, bgs_stream_t stream);
+
 /* Polygon ground truths as COCO run lengths (csrc/poly_rle.hip): rleFrPoly + rleMerge of pycocotools' maskApi.c
  * (mask.frPyObjects then mask.merge, as LoadAnnotations._poly2mask and LVIS.ann_to_rle call them) for all objects of a
  * batch, in a number of launches that does not depend on the batch.  The arithmetic contract is the restatement in
