@@ -4,14 +4,16 @@ Hand-written gfx950 HIP kernels behind a C ABI (``include/bgs.h`` -> ``libbgs.so
 from PyTorch-ROCm through the reference's own registry keys and config schema.
 """
 from . import (backbone, bbox_heads, checkpoint, config, detectors, gs_tables, losses, lvis_eval,  # noqa: F401
-               mask_heads, recall, roi_extractor, rpn, semantic_head, tnorm, train)  # (imports populate the registries)
+               mask_heads, ncm, recall, roi_extractor, rpn, semantic_head, tnorm, train)  # (imports populate the registries)
 from .apis import inference_detector, init_detector
 from .builder import (build_backbone, build_detector, build_head, build_loss, build_neck,
                       build_roi_extractor, build_shared_head)
-from .bbox_heads import ReweightBBoxHead
+from .bbox_heads import DCMBBoxHead, ReweightBBoxHead
 from .config import Config, ConfigDict
-from .functional import sigmoid_focal_loss, sigmoid_focal_loss_elementwise
+from .detectors import DCM
+from .functional import class_sum, ncm_score, sigmoid_focal_loss, sigmoid_focal_loss_elementwise
 from .losses import FocalLoss
+from .ncm import ClassCenters, load_centers
 from .lvis_eval import LVISEval, LVISGroundTruth, ResultArrays, results2arrays, results2json
 from .ops import (DeformConv, DeformConvPack, ModulatedDeformConv, ModulatedDeformConvPack, deform_conv,
                   modulated_deform_conv)
@@ -34,4 +36,5 @@ __all__ = ['BACKBONES', 'DETECTORS', 'HEADS', 'LOSSES', 'NECKS', 'ROI_EXTRACTORS
            'modulated_deform_conv', 'FocalLoss', 'ReweightBBoxHead', 'sigmoid_focal_loss',
            'sigmoid_focal_loss_elementwise', 'tnorm', 'ProposalAccuracy', 'reweight_cls_newhead', 'tail_mask',
            'ResultArrays', 'results2arrays', 'packed2arrays', 'recall', 'eval_recalls', 'lvis_fast_eval_recall',
-           'lvis_fast_eval_recall_percat', 'print_recall_summary', 'proposal2json']
+           'lvis_fast_eval_recall_percat', 'print_recall_summary', 'proposal2json', 'ncm', 'DCM',
+           'DCMBBoxHead', 'ClassCenters', 'load_centers', 'class_sum', 'ncm_score']

@@ -6,6 +6,7 @@ Keys / ctor kwargs / method signatures / state-dict names follow the reference s
 * ``BBoxHead``            mmdet/models/bbox_heads/bbox_head.py:14-239
 * ``ConvFCBBoxHead``      mmdet/models/bbox_heads/convfc_bbox_head.py:8-168
 * ``SharedFCBBoxHead``    mmdet/models/bbox_heads/convfc_bbox_head.py:171-185
+* ``DCMBBoxHead``         mmdet/models/bbox_heads/DCM_bbox_head.py:15-84
 * ``GSBBoxHeadWith0``     mmdet/models/bbox_heads/gs_bbox_head_with0.py:15-380
 * ``GSBBoxHeadWith0Reweight``  mmdet/models/bbox_heads/gs_bbox_head_with0_reweight.py
 * ``GSBBoxHead``          alias of ``GSBBoxHeadWith0`` (no source in the reference tree, only
@@ -324,7 +325,12 @@ class ConvFCBBoxHead(BBoxHead):
         return self._fc1_perm
 
     def forward(self, x, nhwc=False, reg_labels=None):
-        """``x``: RoI features ``[K, C, h, w]`` (reference layout) or, with ``nhwc=True``,
+        return self._forward(x, nhwc, reg_labels)[:2]
+
+    def _forward(self, x, nhwc=False, reg_labels=None):
+        """-> ``(cls_score, bbox_pred, shared)``, ``shared`` being the activation behind the shared FCs (post-ReLU), the
+        tensor the class and box branches read.
+        ``x``: RoI features ``[K, C, h, w]`` (reference layout) or, with ``nhwc=True``,
         ``[K, h, w, C]`` as produced by our RoIAlign.  Every FC runs in the MFMA GEMM kernel (bias +
         ReLU fused).  (torch restatement for the CPU checks: oracle/tensor_forms.convfc_bbox_forward.)
 
@@ -354,7 +360,7 @@ class ConvFCBBoxHead(BBoxHead):
             first, hidden = False, True
         if nhwc and self.num_shared_fcs == 0:
             raise NotImplementedError('NHWC RoI features need a shared first FC')
-        x_cls = x_reg = x
+        x_cls = x_reg = shared = x
         h_cls = h_reg = hidden
         for fc in self.cls_fcs:
             x_cls = fc_apply(fc, x_cls, True, False, h_cls)
@@ -369,7 +375,7 @@ class ConvFCBBoxHead(BBoxHead):
                 not (torch.is_grad_enabled() and (x_reg.requires_grad or self.fc_reg.weight.requires_grad or
                                                   (self.fc_reg.bias is not None and self.fc_reg.bias.requires_grad))):
             cls_score = fc_apply(self.fc_cls, x_cls, False, False, h_cls) if self.with_cls else None
-            return cls_score, BF.fc_reg_gather(x_reg, self.fc_reg.weight, self.fc_reg.bias, reg_labels)
+            return cls_score, BF.fc_reg_gather(x_reg, self.fc_reg.weight, self.fc_reg.bias, reg_labels), shared
         if self.with_cls and self.with_reg and not self.reg_fcs and BF.shortcut_fork_enabled() and \
                 not (torch.is_grad_enabled() and (x_reg.requires_grad or self.fc_reg.weight.requires_grad)):
             with BF.forked(x_reg.device) as fk:
@@ -379,7 +385,7 @@ class ConvFCBBoxHead(BBoxHead):
             fk.join()
         else:
             bbox_pred = fc_apply(self.fc_reg, x_reg, False, False, h_reg) if self.with_reg else None
-        return cls_score, bbox_pred
+        return cls_score, bbox_pred, shared
 
 
 @HEADS.register_module
@@ -390,6 +396,21 @@ class SharedFCBBoxHead(ConvFCBBoxHead):
         super().__init__(num_shared_convs=0, num_shared_fcs=num_fcs, num_cls_convs=0,
                          num_cls_fcs=0, num_reg_convs=0, num_reg_fcs=0,
                          fc_out_channels=fc_out_channels, *args, **kwargs)
+
+
+@HEADS.register_module
+class DCMBBoxHead(SharedFCBBoxHead):
+    """``SharedFCBBoxHead`` whose ``forward`` also returns the feature the NCM classifier reads
+    (DCM_bbox_head.py:15-84).  The reference names that third output ``before_relu``, but its ``self.relu`` works in
+    place: what it returns is the post-ReLU activation of the last shared FC, the very tensor ``fc_cls`` reads, and that
+    executed behaviour is the contract here.  ``get_det_bboxes`` takes READY scores (:61, no softmax): the detector
+    has already combined the background probability with the NCM scores."""
+
+    def forward(self, x, nhwc=False, reg_labels=None):
+        return self._forward(x, nhwc, reg_labels)
+
+    def _scores(self, cls_score):
+        return cls_score
 
 
 @HEADS.register_module

@@ -306,6 +306,10 @@ SIGNATURES = {
     'bgs_score_reweight_select': (ctypes.c_int, [c_f32p, c_f32p, c_ptr, c_ptr, ctypes.c_int, ctypes.c_int, c_f32p,
                                                  c_ptr, c_ptr]),
     'bgs_cls_acc_count': (ctypes.c_int, [c_ptr, c_ptr, ctypes.c_int, ctypes.c_int, c_ptr, c_ptr, c_ptr]),
+    'bgs_class_sum_max_rows': (ctypes.c_int, []),
+    'bgs_class_sum': (ctypes.c_int, [c_f32p, c_i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_ptr, c_i64p, c_ptr]),
+    'bgs_ncm_score': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_ptr, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p,
+                                     c_ptr, c_ptr]),
 }
 
 _LIB = None

@@ -401,18 +401,26 @@ class TwoStageDetector(nn.Module):
         scores + decoded boxes -> one batched 1230-class NMS.  The cascades (cascade_rcnn.py:300-393,
         htc.py:313-377, ensemble result): ``_box_scores`` is their stage loop."""
         rois, valid = self._image_proposals(proposals)
-        if self.use_reweight:
-            bboxes, scores, _ = self._reweighted_scores(x, rois, valid, img_meta, rescale)
-        else:
-            rois, cls_score, bbox_pred = self._box_scores(x, ctx, rois, img_meta)
-            bboxes, scores = self._last_bbox_head.get_det_bboxes(
-                rois, cls_score, bbox_pred, img_meta[0]['img_shape'], img_meta[0]['scale_factor'],
-                rescale=rescale, cfg=None)
+        bboxes, scores, _ = self._proposal_scores(x, ctx, rois, valid, img_meta, rescale)
         if valid is not None:        # padding rows of the fixed-shape proposal list never survive
             scores = torch.where(valid[:, None], scores, scores.new_full((), -1.0))
         det_bboxes, det_labels = PP.multiclass_nms(bboxes, scores, rcnn_test_cfg.score_thr,
                                                    rcnn_test_cfg.nms, rcnn_test_cfg.max_per_img)
         return det_bboxes, det_labels, scores
+
+    _labels_proposals = property(lambda self: self.use_reweight)      # does _proposal_scores return pred_label?
+
+    def _proposal_scores(self, x, ctx, rois, valid, img_meta, rescale):
+        """One image's RoIs -> ``(bboxes, scores [R, C], pred_label [R] int32 | None)``: decoded boxes and the class
+        scores ``multiclass_nms`` takes; ``pred_label`` where the scoring launch gives the arg-max along (the two-head
+        test, DCM)."""
+        if self.use_reweight:
+            return self._reweighted_scores(x, rois, valid, img_meta, rescale)
+        rois, cls_score, bbox_pred = self._box_scores(x, ctx, rois, img_meta)
+        bboxes, scores = self._last_bbox_head.get_det_bboxes(
+            rois, cls_score, bbox_pred, img_meta[0]['img_shape'], img_meta[0]['scale_factor'],
+            rescale=rescale, cfg=None)
+        return bboxes, scores, None
 
     def _reweighted_scores(self, x, rois, valid, img_meta, rescale):
         """test_mixins.py:94-130 (``simple_test_bboxes_reweight`` up to the NMS): both heads on the same RoI features,
@@ -437,7 +445,7 @@ class TwoStageDetector(nn.Module):
         the class the two-head test gives each -> ``(proposals [R, 5], valid [R] | None, pred_label [R] int32)``, all
         on the device; ``pred_label`` is -1 on the padding rows of the fixed-shape proposal list.  Feed them to
         ``tnorm.ProposalAccuracy.update``."""
-        if not self.use_reweight:
+        if not self._labels_proposals:
             raise RuntimeError('classify_proposals needs a model built with test_cfg.test_mode = True')
         self._check_test_cfg()
         with torch.no_grad():
@@ -445,7 +453,7 @@ class TwoStageDetector(nn.Module):
             proposal_list = (self.simple_test_rpn(x, img_meta, self.test_cfg.rpn)
                              if proposals is None else proposals)
             rois, valid = self._image_proposals(proposal_list)
-            _, _, pred_label = self._reweighted_scores(x, rois, valid, img_meta, False)
+            _, _, pred_label = self._proposal_scores(x, None, rois, valid, img_meta, False)
         props = proposal_list[0][0] if isinstance(proposal_list[0], tuple) else proposal_list[0]
         return props, valid, pred_label
 
@@ -722,6 +730,141 @@ class TwoStageDetector(nn.Module):
 @DETECTORS.register_module
 class FasterRCNN(TwoStageDetector):
     pass
+
+
+@DETECTORS.register_module
+class DCM(TwoStageDetector):
+    """mmdet/models/detectors/DCM.py:13-221: Faster R-CNN whose foreground scores come from a nearest-class-mean
+    classifier (configs/transferred/faster_rcnn_r50_fpn_1x_lvis_dcm.py; the ``NCM-fc`` / ``NCM-conv`` rows).
+
+    Test (``simple_test_bboxes`` :178-221, ``simple_test_bboxes0`` :135-175): ``bg = softmax(cls_score)[:, :1]``, the
+    cosine of every proposal's feature with every unit class centre, ``cat([bg, (1 - bg) * softmax(cos)])``, then the
+    head's box decoding and ``multiclass_nms``: here RoIAlign -> ``DCMBBoxHead`` -> one GEMM -> one launch
+    (``functional.ncm_score``).  Collection (``forward_train`` :82-109, run for one epoch at ``lr = 0``): the features at
+    the GROUND-TRUTH boxes go into the ``ncm.ClassCenters`` attached with :meth:`collect_into`, one launch each, instead
+    of three files per image.
+
+    ``test_cfg`` keys (this package's extensions, as ``reweight_mask`` is):
+      ``dcm_centers``  the centres file in the reference's layout; default: the path the reference hard-codes (:39).
+                       ``None`` builds a collection-only model: ``simple_test`` raises.
+      ``dcm_feature``  ``'conv'`` (default; the reference's live method: the pooled RoI feature, 256 x 7 x 7) or
+                       ``'fc'`` (``simple_test_bboxes0``: the last shared FC activation).
+    The centres are a plain attribute as in the reference: the state dict is ``FasterRCNN``'s."""
+
+    DCM_CENTERS = './data/lvis/dcm_center_fea.pt'
+    DCM_FEATURES = ('conv', 'fc')
+    _labels_proposals = True
+
+    def __init__(self, backbone, rpn_head, bbox_roi_extractor, bbox_head, train_cfg, test_cfg, neck=None,
+                 shared_head=None, pretrained=None):
+        if test_cfg is not None and test_cfg.get('test_mode', False):
+            raise NotImplementedError('DCM: test_cfg.test_mode (the two-head test) is not part of the NCM baseline')
+        feature = test_cfg.get('dcm_feature', 'conv') if test_cfg is not None else 'conv'
+        if feature not in self.DCM_FEATURES:
+            raise ValueError("DCM: test_cfg.dcm_feature must be 'conv' or 'fc', got %r" % (feature,))
+        super().__init__(backbone=backbone, neck=neck, shared_head=shared_head, rpn_head=rpn_head,
+                         bbox_roi_extractor=bbox_roi_extractor, bbox_head=bbox_head, train_cfg=train_cfg,
+                         test_cfg=test_cfg, pretrained=pretrained)
+        from .bbox_heads import DCMBBoxHead
+        if not isinstance(self.bbox_head, DCMBBoxHead):
+            raise TypeError('DCM needs a box head whose forward returns (cls_score, bbox_pred, fea): DCMBBoxHead, '
+                            'got %s' % type(self.bbox_head).__name__)
+        self.dcm_feature = feature
+        self.unit_centers = None
+        self._collectors = dict(conv=None, fc=None)
+        path = test_cfg.get('dcm_centers', self.DCM_CENTERS) if test_cfg is not None else None
+        if path is not None:
+            self.load_centers(path)
+
+    def feature_dims(self):
+        """``dict(conv=256 * 7 * 7, fc=1024)`` for the shipped head."""
+        h = self.bbox_head
+        return dict(conv=h.in_channels * h.roi_feat_area, fc=h.fc_out_channels)
+
+    def _feature_layout(self, which):
+        return dict(layout='chw' if which == 'conv' else 'flat', spatial=self.bbox_head.roi_feat_area)
+
+    def load_centers(self, path):
+        """``DCM.__init__`` :39-42 for ``test_cfg.dcm_feature``: ``ncm.load_centers``; the file must hold one centre per
+        class of the head in the width of that feature (``ValueError``)."""
+        from . import ncm
+        want = (self.bbox_head.num_classes, self.feature_dims()[self.dcm_feature])     # (dcm_feature decides the width)
+        unit = ncm.load_centers(path, expect=want, **self._feature_layout(self.dcm_feature))
+        self.unit_centers = unit
+        return self
+
+    def _centers_on(self, device):
+        if self.unit_centers.device != device:
+            self.unit_centers = self.unit_centers.to(device)
+        return self.unit_centers
+
+    def _check_test_cfg(self):
+        if self.unit_centers is None:
+            raise RuntimeError('DCM: built with test_cfg.dcm_centers = None (collection only); simple_test needs the '
+                               'class centres (load_centers(path))')
+
+    def _proposal_scores(self, x, ctx, rois, valid, img_meta, rescale):
+        feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
+        cls_score, bbox_pred, fc_fea = self.bbox_head(feats, nhwc=True)
+        fea = feats.reshape(feats.shape[0], -1).contiguous() if self.dcm_feature == 'conv' else fc_fea
+        cls_score = cls_score.contiguous()
+        scores, pred_label = BF.ncm_score(fea, self._centers_on(fea.device), cls_score, valid=valid, out=cls_score)
+        bboxes, scores = self.bbox_head.get_det_bboxes(rois, scores, bbox_pred, img_meta[0]['img_shape'],
+                                                       img_meta[0]['scale_factor'], rescale=rescale, cfg=None)
+        return bboxes, scores, pred_label
+
+    # -- collection ---------------------------------------------------------------------------------------------
+    def collect_into(self, conv=None, fc=None):
+        """Attach the ``ncm.ClassCenters`` that ``forward_train`` updates (``None`` detaches)."""
+        dims = self.feature_dims()
+        for which, cc in (('conv', conv), ('fc', fc)):
+            if cc is not None and (cc.dim != dims[which] or cc.num_classes != self.bbox_head.num_classes or
+                                   cc.layout != self._feature_layout(which)['layout']):
+                raise ValueError('DCM.collect_into: %s needs ClassCenters(%d, %d, layout=%r), got (%d, %d, %r)'
+                                 % (which, self.bbox_head.num_classes, dims[which],
+                                    self._feature_layout(which)['layout'], cc.num_classes, cc.dim, cc.layout))
+            self._collectors[which] = cc
+        return self
+
+    def _collect(self, x, gt_bboxes, gt_labels):
+        """DCM.py:87-103 -> ``(cls_score, conv_fea [G, 7, 7, C], fc_fea [G, F], labels [G])``."""
+        rois = torch.cat([torch.cat([b.new_full((b.size(0), 1), float(i)), b[:, :4]], dim=1)
+                          for i, b in enumerate(gt_bboxes)]).float().contiguous()
+        labels = torch.cat(list(gt_labels), dim=0)
+        if rois.shape[0] == 0:
+            h = self.bbox_head
+            return (rois.new_zeros((0, h.num_classes)), rois.new_zeros((0,) + h.roi_feat_size + (h.in_channels,)),
+                    rois.new_zeros((0, h.fc_out_channels)), labels)
+        feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
+        cls_score, _, fc_fea = self.bbox_head(feats, nhwc=True)
+        return cls_score, feats, fc_fea, labels
+
+    def collect_features(self, img, img_meta, gt_bboxes, gt_labels, feats=None):
+        """The three tensors the reference saves per image (DCM.py:93-105), on the device: RoIAlign AT THE GROUND-TRUTH
+        BOXES, the head -> ``(conv_fea [G, 7, 7, C], fc_fea [G, F], labels [G])``."""
+        with torch.no_grad():
+            x = self.extract_feat(img) if feats is None else feats
+            return self._collect(x, gt_bboxes, gt_labels)[1:]
+
+    def forward_train(self, img, img_meta, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None,
+                      proposals=None, feats=None):
+        """DCM.py:45-109: ``dict(loss=cls_score)`` of the head at the ground-truth boxes (the config trains at
+        ``lr = 0``); the attached ``ClassCenters`` take the features.  No file, no host read."""
+        x = self.extract_feat(img) if feats is None else feats
+        cls_score, conv_fea, fc_fea, labels = self._collect(x, gt_bboxes, gt_labels)
+        if labels.numel():
+            if self._collectors['conv'] is not None:
+                self._collectors['conv'].update(conv_fea, labels)
+            if self._collectors['fc'] is not None:
+                self._collectors['fc'].update(fc_fea, labels)
+        return dict(loss=cls_score)
+
+    # -- what the reference's DCM does not have -------------------------------------------------------------------
+    def aug_test(self, imgs, img_metas, **kwargs):
+        raise NotImplementedError('DCM.aug_test: the NCM baseline is simple_test ground (one image, one view)')
+
+    def simple_test_batch(self, img, img_metas, **kwargs):
+        raise NotImplementedError('DCM.simple_test_batch: the NCM baseline is simple_test ground (one image per pass)')
 
 
 @DETECTORS.register_module

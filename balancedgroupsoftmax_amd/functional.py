@@ -644,6 +644,87 @@ def cls_acc_count(pred_label, assigned_label, num_ins, num_get):
 
 
 # ----------------------------------------------------------------------------------------
+# NCM baseline  (mmdet/models/detectors/DCM.py; csrc/ncm.hip)
+# ----------------------------------------------------------------------------------------
+def class_sum_max_rows():
+    """Rows one ``class_sum`` call takes (the labels of a call live in LDS)."""
+    return int(capi.load().bgs_class_sum_max_rows())
+
+
+def class_sum(fea, labels, sums, counts):
+    """``sums[labels[g]] += fea[g]`` and ``counts[labels[g]] += 1`` in ascending ``g``, one rounded float64 add per
+    row (bit-identical to ``np.add.at`` on float64; no atomics).  ``fea [G, D]`` float32, ``labels [G]`` int64,
+    ``sums [C, D]`` float64 and ``counts [C]`` int64, both updated in place and returned.  Rows labelled outside
+    ``[0, C)`` are skipped.  At most :func:`class_sum_max_rows` rows per call."""
+    _require_cuda(fea, labels, sums, counts)
+    _require_f32('class_sum', fea=fea)
+    if labels.dtype != torch.int64:
+        raise NotImplementedError('class_sum: labels is %s; int64 is what the kernel reads' % (labels.dtype,))
+    if sums.dtype != torch.float64 or counts.dtype != torch.int64:
+        raise NotImplementedError('class_sum: sums must be float64 and counts int64, got %s and %s'
+                                  % (sums.dtype, counts.dtype))
+    if fea.dim() != 2 or sums.dim() != 2 or fea.shape[1] != sums.shape[1] or fea.shape[1] < 1:
+        raise ValueError('class_sum: fea %s and sums %s must be [G, D] and [C, D]'
+                         % (tuple(fea.shape), tuple(sums.shape)))
+    G, D = fea.shape
+    C = sums.shape[0]
+    if labels.dim() != 1 or labels.numel() != G or counts.dim() != 1 or counts.numel() != C:
+        raise ValueError('class_sum: labels must be [%d] and counts [%d], got %s and %s'
+                         % (G, C, tuple(labels.shape), tuple(counts.shape)))
+    for arg, t in (('fea', fea), ('labels', labels), ('sums', sums), ('counts', counts)):
+        if not t.is_contiguous():
+            raise ValueError('class_sum: %s must be contiguous' % arg)
+    rc = capi.load().bgs_class_sum(capi.ptr(fea.detach()), capi.ptr(labels), G, D, C, capi.ptr(sums), capi.ptr(counts),
+                                   capi.current_stream(fea.device))
+    capi.check('bgs_class_sum', rc)
+    return sums, counts
+
+
+def ncm_score(fea, unit_centres, cls_score, valid=None, out=None):
+    """The scoring lines of ``DCM.simple_test_bboxes`` (DCM.py:192-203): one GEMM (:func:`linear`) and one launch.
+    ``fea [R, D]``, ``unit_centres [C - 1, D]`` (the unit-norm foreground centres, ``ncm.load_centers``),
+    ``cls_score [R, C]`` -> ``(out [R, C], pred_label [R] int32)`` with ``out[:, 0] = softmax(cls_score)[:, 0]``,
+    ``out[:, 1:] = (1 - out[:, :1]) * softmax(cos(fea, centres))`` and ``pred_label = argmax(out, 1)`` (torch's CPU
+    rule), -1 where ``valid [R]`` is 0.  ``out`` may be ``cls_score`` itself; a fresh tensor by default."""
+    _require_cuda(fea, unit_centres, cls_score, valid, out)
+    _require_f32('ncm_score', fea=fea, unit_centres=unit_centres, cls_score=cls_score)
+    if fea.dim() != 2 or unit_centres.dim() != 2 or cls_score.dim() != 2:
+        raise ValueError('ncm_score: fea, unit_centres and cls_score must be matrices')
+    R, D = fea.shape
+    C = cls_score.shape[1]
+    if D < 1 or C < 2 or tuple(unit_centres.shape) != (C - 1, D) or cls_score.shape[0] != R:
+        raise ValueError('ncm_score: fea %s, unit_centres %s and cls_score %s must be [R, D], [C - 1, D] and [R, C]'
+                         % (tuple(fea.shape), tuple(unit_centres.shape), tuple(cls_score.shape)))
+    for arg, t in (('fea', fea), ('unit_centres', unit_centres), ('cls_score', cls_score)):
+        if not t.is_contiguous():
+            raise ValueError('ncm_score: %s must be contiguous' % arg)
+    v = None if valid is None else _u8c('ncm_score', 'valid', valid, R)
+    f, s = fea.detach(), cls_score.detach()
+    if out is None:
+        out = torch.empty_like(s)
+    else:
+        _require_f32('ncm_score', out=out)
+        if tuple(out.shape) != (R, C) or not out.is_contiguous():
+            raise ValueError('ncm_score: out must be a contiguous [R, C] tensor')
+    pred = torch.empty((R,), dtype=torch.int32, device=s.device)
+    if R == 0:
+        return out, pred
+    fg, cg = f, unit_centres.detach()
+    if D % 4 != 0:
+        # the GEMM kernel reads K in 16-byte pieces: zero columns leave every dot product as it is (the norm below is
+        # taken of the feature itself); the detector's widths (12544, 1024) never come here
+        fg = torch.nn.functional.pad(fg, (0, 4 - D % 4))
+        cg = torch.nn.functional.pad(cg, (0, 4 - D % 4))
+    elif fg.data_ptr() % 16 != 0:
+        fg = fg.clone()
+    dots = linear(fg, cg, frozen_weight=D % 4 == 0 and not unit_centres.requires_grad)
+    rc = capi.load().bgs_ncm_score(capi.ptr(f), capi.ptr(dots), capi.ptr(s), capi.ptr(v), R, D, C, capi.ptr(out),
+                                   capi.ptr(pred), capi.current_stream(s.device))
+    capi.check('bgs_ncm_score', rc)
+    return out, pred
+
+
+# ----------------------------------------------------------------------------------------
 # box regression loss  (loss_bbox branch, :173-185)
 # ----------------------------------------------------------------------------------------
 class _BBoxSmoothL1(torch.autograd.Function):

@@ -1236,6 +1236,35 @@ int bgs_score_reweight_select(const float* scores, const float* scores_rw, const
 int bgs_cls_acc_count(const int* pred_label, const int* assigned_label, int R, int C, long long* num_ins,
                       long long* num_get, bgs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * The NCM (nearest-class-mean) baseline of the reference's DCM detector (csrc/ncm.hip).
+ *   class_sum: the per-class feature sums behind the class centres (the reference writes every image's features to
+ *     files, DCM.py:93-105, and averages them on the host): sums[labels[g], :] += fea[g, :] and
+ *     counts[labels[g]] += 1.  fea [G, D] float, labels [G] int64, sums [C, D] double and counts [C] int64 in-out.
+ *     The result is DEFINED as the existing value plus the rows in ascending g, one rounded double add each (what
+ *     np.add.at gives on float64): no atomics, two calls return the same bits.  A row whose label is outside [0, C)
+ *     is skipped.  Any D: 16-byte accesses when D % 4 == 0 and fea / sums are 16-byte aligned, dword loads and
+ *     8-byte stores otherwise.  Limits: G <= bgs_class_sum_max_rows() = 4096 rows per call (the labels and the
+ *     per-class row links of a call live in LDS; a longer batch is fed in pieces, which keeps the order):
+ *     BGS_ERR_UNSUPPORTED beyond, before anything is launched.  fea 4-byte, labels / sums / counts 8-byte aligned
+ *     (BGS_ERR_INVALID_ARG otherwise).  G == 0 is BGS_OK and touches nothing.
+ *   ncm_score: the scoring lines of DCM.simple_test_bboxes (DCM.py:192-203) after the GEMM, one wave per row, one
+ *     launch, no host read.  fea [R, D] (the feature the centres were taken of), dots [R, C - 1] = fea @
+ *     unit_centres^T, cls_score [R, C] (the head's logits), valid [R] uint8 or NULL:
+ *       bg = softmax(cls_score[r])[0];  cos_j = dots[r, j] / ||fea[r]||_2;  p = softmax(cos)
+ *       out[r, 0] = bg;  out[r, 1 + j] = (1 - bg) * p_j;  pred_label[r] = argmax(out[r]), -1 where valid[r] == 0
+ *     in double on the float inputs (the squares summed in a fixed order), every element rounded once.  The arg-max
+ *     is torch's CPU rule (first maximum, a NaN counts as the maximum).  A zero feature row gives NaN in columns
+ *     1 .. C - 1, as the reference's 0 / 0 does, and a finite out[r, 0].  out [R, C] float may be cls_score;
+ *     pred_label [R] int32.  Any D >= 1, C >= 2 (BGS_ERR_INVALID_ARG otherwise); rows need not be 16-byte aligned.
+ *     R == 0 is BGS_OK.
+ * ---------------------------------------------------------------------------------- */
+int bgs_class_sum_max_rows(void);
+int bgs_class_sum(const float* fea, const long long* labels, int G, int D, int C, double* sums, long long* counts,
+                  bgs_stream_t stream);
+int bgs_ncm_score(const float* fea, const float* dots, const float* cls_score, const uint8_t* valid, int R, int D,
+                  int C, float* out, int* pred_label, bgs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
