@@ -15,7 +15,12 @@ oracle/tensor_forms.py).
 Test time: ``TwoStageDetector`` owns the three flows (``simple_test``, ``simple_test_batch``, ``aug_test``: checks, a
 device-tensor core, ``bbox2result``); ``CascadeRCNN`` and ``HybridTaskCascade`` supply the pieces that differ (the stage
 loop as ``_box_scores``, the per-stage mask probabilities, the semantic feature as per-pass context).
+
+Training has the same shape: ``TwoStageDetector`` owns the RPN part, the RoI sampling and the mask-branch inputs,
+``CascadeRCNN`` the one stage loop; HTC supplies hooks.  No step keeps a result on the module: it returns it.
 """
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
 
@@ -24,6 +29,11 @@ from . import functional as BF
 from . import post_processing as PP
 from .registry import DETECTORS
 
+
+# SamplingResult in fixed shape: ``targets`` = ``(labels, label_weights, bbox_targets, bbox_weights)``; per slot
+# ``[N, num]`` the assigned GT index (-1 = none), whether the slot is real (not padding) and whether it is a GT box added
+# as a proposal (``pos_is_gt``): these three are ``None`` for the plain box detectors, where nobody reads them.
+RoISamples = namedtuple('RoISamples', ['rois', 'targets', 'gt_inds', 'valid', 'is_gt'])
 
 _GT_ROWS = {}
 
@@ -136,7 +146,7 @@ class TwoStageDetector(nn.Module):
         one kernel that emits rois / labels / box targets for all images.
         ``rc`` / ``head``: the stage's rcnn config and bbox head (cascade); defaults: the
         detector's own.  ``samplers``: test hook (``dict(rcnn=fn)``: a caller-supplied draw
-        instead of the device RandomSampler; oracle/tensor_forms.sampler_hooks)."""
+        instead of the device RandomSampler; oracle/tensor_forms.sampler_hooks).  -> ``RoISamples``."""
         rc = self.train_cfg.rcnn if rc is None else rc
         ac, sc = rc.assigner, rc.sampler
         N = len(proposal_list)
@@ -155,6 +165,10 @@ class TwoStageDetector(nn.Module):
                                  ac.get('min_pos_iou', 0.0), valid=pvalid, shared_boxes=False)
         add_gt = sc.get('add_gt_as_proposals', True)
         rcnn_hook = samplers.get('rcnn') if samplers else None
+        # only the mask branch and the cascade refinement read gt_inds / valid / is_gt: the plain box detectors
+        # launch bgs_sample_rois (not _ex), and under the test hook skip ~10 small launches
+        need_extra = self.with_mask or isinstance(self.bbox_head, nn.ModuleList)
+        gt_inds = valid = is_gt = None
         boxes_l, assigned_l, inds_l, valid_l = [], [], [], []
         for i in range(N):
             b, a = props[i, :, :4], assigned[i]
@@ -165,49 +179,38 @@ class TwoStageDetector(nn.Module):
             boxes_l.append(b.contiguous())
             assigned_l.append(a.contiguous())
             if rcnn_hook is not None:      # test hook: caller-supplied draw
-                inds, _, valid = rcnn_hook(a, sc.num, sc.pos_fraction)
+                inds, _, v = rcnn_hook(a, sc.num, sc.pos_fraction)
                 inds_l.append(inds.contiguous())
-                valid_l.append(valid)
+                valid_l.append(v)
         if rcnn_hook is None:
             if any(a.numel() > 4096 for a in assigned_l):
                 raise NotImplementedError('bgs_sample_rois sorts <= 4096 candidates per image in LDS '
                                           '(rpn_proposal.max_num + GT boxes)')
             # one launch for the batch (csrc/sampler.hip: sort of (class, random key) composites)
-            need_extra = self.with_mask or isinstance(self.bbox_head, nn.ModuleList)
             res = BF.sample_rois(assigned_l, sc.num, sc.pos_fraction,
                                  gt_counts=[int(g.size(0)) if add_gt else 0 for g in gt_bboxes]
                                  if need_extra else None)
             inds_all, valid_all = res[0], res[2].view(torch.bool)
             inds_l = [inds_all[i] for i in range(N)]
             valid_l = [valid_all[i] for i in range(N)]
-            if need_extra:
-                # what the mask branch and the cascade refinement read from the SamplingResult come out
-                # of the sampling launch itself (bgs_sample_rois_ex) instead of ~13 gather / compare /
-                # stack launches per stage
-                self._sampled_gt_inds = res[3]
-                self._sampled_valid = valid_all
-                self._sampled_is_gt = res[4].view(torch.bool)
-        if rcnn_hook is not None and (self.with_mask or isinstance(self.bbox_head, nn.ModuleList)):
-            # (only the mask branch and the cascade refinement read these: skipped for the plain
-            #  box detectors, ~10 small launches)
-            # gt index of every sampled RoI (pos_assigned_gt_inds for the mask targets), -1 = none
-            self._sampled_gt_inds = torch.stack(
-                [assigned_l[i].gather(0, inds_l[i]).to(torch.int32) - 1 for i in range(N)])
-            # which sampled RoIs are GT boxes added as proposals (SamplingResult.pos_is_gt), and
-            # which slots are real (fewer candidates than `num` leaves padding slots)
-            self._sampled_valid = torch.stack(valid_l)
-            self._sampled_is_gt = torch.stack(
-                [(inds_l[i] < gt_bboxes[i].size(0)) if add_gt else torch.zeros_like(valid_l[i])
-                 for i in range(N)])
+            if need_extra:      # out of the sampling launch itself (bgs_sample_rois_ex), not ~13 launches per stage
+                gt_inds, valid, is_gt = res[3], valid_all, res[4].view(torch.bool)
+        elif need_extra:
+            # the same from the caller's draw: pos_assigned_gt_inds of every slot, the real slots, pos_is_gt
+            gt_inds = torch.stack([assigned_l[i].gather(0, inds_l[i]).to(torch.int32) - 1 for i in range(N)])
+            valid = torch.stack(valid_l)
+            is_gt = torch.stack([(inds_l[i] < gt_bboxes[i].size(0)) if add_gt else torch.zeros_like(valid_l[i])
+                                 for i in range(N)])
         head = self.bbox_head if head is None else head
         rois, labels, lw, bt, bw = BF.rcnn_targets(
             boxes_l, assigned_l, inds_l, valid_l, [g.contiguous() for g in gt_labels], gt_cat, offs,
             sc.num, head.target_means, head.target_stds, rc.pos_weight)
-        return rois, (labels, lw, bt, bw)
+        return RoISamples(rois, (labels, lw, bt, bw), gt_inds, valid, is_gt)
 
     # -- RPN part of a training iteration ------------------------------------------------------
     def _rpn_forward_train(self, x, img_meta, gt_bboxes, proposals, samplers, losses, fork_loss=False):
-        """RPN losses + the fixed-shape proposal list (two_stage.py:157-176).
+        """RPN losses + the fixed-shape proposal list (two_stage.py:157-176) -> ``(proposal_list, fork)``: the RPN
+        loss chain left running on its side stream (``fork_loss``) or ``None``; the caller joins it in a ``finally``.
 
         (Measured and dropped: launching the loss branch — anchor assignment, sampler, BCE +
         SmoothL1 sums, ~0.45 ms of small latency-bound kernels that only read the RPN outputs — on
@@ -215,23 +218,22 @@ class TwoStageDetector(nn.Module):
         graph replays, but 12.00 vs 12.05 ms: the replayed graph does not run the two branches
         concurrently, and eager launches are host-bound.  profiles/r2w_*.)"""
         if not self.with_rpn:
-            return [(p, torch.ones(p.size(0), dtype=torch.bool, device=p.device)) for p in proposals]
+            return [(p, torch.ones(p.size(0), dtype=torch.bool, device=p.device)) for p in proposals], None
         cls_scores, bbox_preds = self.rpn_head(x)
-        self._rpn_loss_fork = None
+        fork = None
         if fork_loss and cls_scores[0].is_cuda and BF.rpn_loss_fork_enabled() and not samplers and \
                 not (torch.is_grad_enabled() and cls_scores[0].requires_grad):
             # the RPN loss chain (anchor assignment, sampler, BCE + SmoothL1 sums: ~12 short launches that only
-            # read the RPN outputs) beside the proposal -> RoI-head chain; joined in forward_train before the
+            # read the RPN outputs) beside the proposal -> RoI-head chain; joined by the caller before the
             # losses are returned.  (Round 2 measured no gain: the step was 560 launches and eager launching was
             # host-bound; at 150 launches it is not.)
-            with BF.forked(cls_scores[0].device, lane=1) as fk:
+            with BF.forked(cls_scores[0].device, lane=1) as fork:
                 losses.update(self.rpn_head.loss(cls_scores, bbox_preds, gt_bboxes, img_meta,
                                                  self.train_cfg.rpn, samplers=samplers))
             # the chain reads the RPN outputs (main / lane-0 pools) long after this function has dropped its
-            # references (``_fused = None`` below, the return): held until ``_join_rpn_loss`` so that the caching
+            # references (``_fused = None`` below, the return): held until the caller's join so that the caching
             # allocator cannot hand their blocks to the RoI stage while ``rpn_loss_kernel`` is still reading them
-            fk.hold(cls_scores, bbox_preds, self.rpn_head._fused, gt_bboxes)
-            self._rpn_loss_fork = fk
+            fork.hold(cls_scores, bbox_preds, self.rpn_head._fused, gt_bboxes)
         else:
             losses.update(self.rpn_head.loss(cls_scores, bbox_preds, gt_bboxes, img_meta,
                                              self.train_cfg.rpn, samplers=samplers))
@@ -249,14 +251,7 @@ class TwoStageDetector(nn.Module):
         # trunk trains (selectp=0): drop it, or the graph (and its AccumulateGrad nodes, bound to
         # the stream they were created on) would outlive the iteration
         self.rpn_head._fused = None
-        return proposal_list
-
-    def _join_rpn_loss(self):
-        """Make the current stream wait for the RPN loss chain launched beside it (see _rpn_forward_train)."""
-        fk = getattr(self, '_rpn_loss_fork', None)
-        if fk is not None:
-            fk.join()
-            self._rpn_loss_fork = None
+        return proposal_list, fork
 
     def trunk_is_frozen(self):
         """True when no parameter of the backbone / neck trains (the shipped ``selectp = 1`` / ``3``): their features
@@ -270,60 +265,67 @@ class TwoStageDetector(nn.Module):
         # ``feats``: the output of ``extract_feat(img)`` computed ahead of this call (train.TrunkPipeline)
         x = self.extract_feat(img) if feats is None else feats
         losses = dict()
-        proposal_list = self._rpn_forward_train(x, img_meta, gt_bboxes, proposals, samplers, losses,
-                                                fork_loss=True)      # (joined below)
-        if self.with_bbox:
-            if not self.train_cfg.rcnn.assigner.get('gt_max_assign_all', True):
-                raise NotImplementedError('gt_max_assign_all=False')
-            rois, targets = self._sample_rois_fused(proposal_list, gt_bboxes, gt_labels, samplers)
-            mask_fk = None
-            if self.with_mask and rois.is_cuda and BF.rpn_loss_fork_enabled() and not (
-                    torch.is_grad_enabled() and any(p.requires_grad for p in self.mask_head.parameters())):
-                # frozen mask branch (mask RoIAlign, four convs, deconv, targets, BCE): independent of the box
-                # head — beside it on its own stream when the step is launched eagerly
-                with BF.forked(rois.device, lane=2) as mask_fk:
-                    mask_losses = self._mask_forward_train(x, rois, targets[0], gt_masks, img.size(0))
-                mask_fk.hold(x, rois, targets, gt_masks)
-            bbox_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
-            cls_score, bbox_pred = self.bbox_head(bbox_feats, nhwc=True, reg_labels=targets[0])
-            losses.update(self.bbox_head.loss(cls_score, bbox_pred, *targets))
-            if mask_fk is not None:
-                mask_fk.join()
-                losses.update(mask_losses)
+        proposal_list, rpn_fork = self._rpn_forward_train(x, img_meta, gt_bboxes, proposals, samplers, losses,
+                                                          fork_loss=True)
+        try:
+            if self.with_bbox:
+                if not self.train_cfg.rcnn.assigner.get('gt_max_assign_all', True):
+                    raise NotImplementedError('gt_max_assign_all=False')
+                samples = self._sample_rois_fused(proposal_list, gt_bboxes, gt_labels, samplers)
+                rois, targets = samples.rois, samples.targets
+                mask_fk = None
+                if self.with_mask and rois.is_cuda and BF.rpn_loss_fork_enabled() and not (
+                        torch.is_grad_enabled() and any(p.requires_grad for p in self.mask_head.parameters())):
+                    # frozen mask branch (mask RoIAlign, four convs, deconv, targets, BCE): independent of the box
+                    # head — beside it on its own stream when the step is launched eagerly
+                    with BF.forked(rois.device, lane=2) as mask_fk:
+                        mask_losses = self._mask_forward_train(x, samples, gt_masks)
+                    mask_fk.hold(x, samples, gt_masks)      # (the record: rois, targets and gt_inds)
+                bbox_feats = self.bbox_roi_extractor(x[:self.bbox_roi_extractor.num_inputs], rois)
+                cls_score, bbox_pred = self.bbox_head(bbox_feats, nhwc=True, reg_labels=targets[0])
+                losses.update(self.bbox_head.loss(cls_score, bbox_pred, *targets))
+                if mask_fk is not None:
+                    mask_fk.join()
+                    losses.update(mask_losses)
+                elif self.with_mask:
+                    losses.update(self._mask_forward_train(x, samples, gt_masks))
             elif self.with_mask:
-                losses.update(self._mask_forward_train(x, rois, targets[0], gt_masks, img.size(0)))
-        elif self.with_mask:
-            losses.update(self._mask_forward_train(x, rois, targets[0], gt_masks, img.size(0)))
-        self._join_rpn_loss()
+                raise NotImplementedError('a mask head without a box head is not on the BAGS path')
+        finally:
+            if rpn_fork is not None:       # also when the RoI stage raised: the side stream is never left unjoined
+                rpn_fork.join()
         return losses
 
-    def _mask_forward_train(self, x, rois, labels, gt_masks, num_imgs):
-        """two_stage.py:228-263 with a FIXED number of mask RoIs: the sampler puts the positives
-        first (at most ``int(num * pos_fraction)`` per image), so the first ``max_pos`` slots of
-        every image are the candidates and ``labels > 0`` says which of them are real; padding
-        slots get zero weight in the mean instead of being filtered out on the host."""
+    def _mask_inputs(self, samples, gt_masks, sc):
+        """What a mask branch trains on, a FIXED number of mask RoIs: the sampler puts the positives first (at most
+        ``int(num * pos_fraction)`` per image), so the first ``max_pos`` slots of every image are the candidates and
+        ``labels > 0`` says which of them are real; padding slots get zero weight in the mean instead of being
+        filtered out on the host.  -> ``(pos_rois, pos_labels, valid, gt_inds, masks)``."""
         if gt_masks is None:
             raise ValueError('the mask branch needs gt_masks (per image a uint8 [G, H, W] tensor)')
+        rois, labels = samples.rois, samples.targets[0]
         if not rois.is_cuda:
             raise NotImplementedError('the mask branch runs on the GPU path only')
-        sc = self.train_cfg.rcnn.sampler
         max_pos = int(sc.num * sc.pos_fraction)
-        num = sc.num
-        sel = (torch.arange(num_imgs, device=rois.device).view(-1, 1) * num +
+        sel = (torch.arange(samples.gt_inds.size(0), device=rois.device).view(-1, 1) * sc.num +
                torch.arange(max_pos, device=rois.device).view(1, -1)).reshape(-1)
         pos_rois = rois[sel].contiguous()
         pos_labels = labels[sel].contiguous()
         valid = pos_labels > 0
-        gt_inds = self._sampled_gt_inds[:, :max_pos].reshape(-1).contiguous()
-        masks = [torch.as_tensor(m).to(device=rois.device, dtype=torch.uint8).contiguous()
-                 for m in gt_masks]
+        gt_inds = samples.gt_inds[:, :max_pos].reshape(-1).contiguous()
+        masks = [torch.as_tensor(m).to(device=rois.device, dtype=torch.uint8).contiguous() for m in gt_masks]
+        return pos_rois, pos_labels, valid, gt_inds, masks
+
+    def _mask_forward_train(self, x, samples, gt_masks):
+        """two_stage.py:228-263 on the fixed-shape positives (``_mask_inputs``)."""
+        rc = self.train_cfg.rcnn
+        pos_rois, pos_labels, valid, gt_inds, masks = self._mask_inputs(samples, gt_masks, rc.sampler)
         if self.share_roi_extractor:
             raise NotImplementedError('share_roi_extractor=True (7x7 features for the mask head) '
                                       'is not used by the BAGS configs')
         mask_feats = self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], pos_rois)
         feats = self.mask_head.features(mask_feats, nhwc=True)
-        mask_targets = self.mask_head.get_target_fixed(pos_rois, gt_inds, valid, masks,
-                                                       self.train_cfg.rcnn)
+        mask_targets = self.mask_head.get_target_fixed(pos_rois, gt_inds, valid, masks, rc)
         return self.mask_head.loss_from_features(feats, mask_targets, pos_labels, valid)
 
     # ------------------------------------------------------------------ test-time path
@@ -939,19 +941,56 @@ class CascadeRCNN(TwoStageDetector):
             for head in self.mask_head:
                 head.init_weights()
 
-    def _refined_proposals(self, head, rois, labels, bbox_pred, img_meta, num):
-        """``refine_bboxes`` (bbox_head.py:169-208) in fixed shape: every sampled RoI re-regressed
+    def _refined_proposals(self, head, samples, bbox_pred, img_meta):
+        """``refine_bboxes`` (bbox_head.py:169-208) in fixed shape: every sampled RoI of ``samples`` re-regressed
         with its target class; GT rows and padding slots are masked instead of removed."""
-        n_img = len(img_meta)
+        n_img, num = samples.valid.shape
         with torch.no_grad():
             # regress_by_class + delta2bbox for every image in ONE launch (csrc/det_targets.hip:
             # refine_boxes_kernel; the tensor form is ~35 element-wise launches per image and stage)
-            boxes = BF.refine_boxes(rois.contiguous(), labels.contiguous(), bbox_pred.detach().contiguous(),
-                                    [m['img_shape'] for m in img_meta], head.target_means,
-                                    head.target_stds)
-            keep = self._sampled_valid & ~self._sampled_is_gt
+            boxes = BF.refine_boxes(samples.rois.contiguous(), samples.targets[0].contiguous(),
+                                    bbox_pred.detach().contiguous(), [m['img_shape'] for m in img_meta],
+                                    head.target_means, head.target_stds)
+            keep = samples.valid & ~samples.is_gt
             from .rpn import ProposalList
             return ProposalList(boxes.view(n_img, num, 4), keep)
+
+    interleaved = False      # HTC: stage i's mask branch trains on the boxes stage i's box head just refined
+
+    def _stage_mask_forward_train(self, stage, x, ctx, samples, refined, gt_bboxes, gt_labels, gt_masks, samplers):
+        """The stage's mask losses (HTC); ``refined``: the stage's refined proposals, or ``None``."""
+        return {}
+
+    def _stages_forward_train(self, x, ctx, proposal_list, img_meta, gt_bboxes, gt_labels, gt_masks, samplers):
+        """The training stage loop (cascade_rcnn.py:207-296 / htc.py:235-306), written once -> the stages' losses as
+        ``s{i}.{name}``.  Per stage, in this order (every sampling launch advances the device draw counter): sample;
+        RoI features (``_bbox_roi_feats``: HTC fuses the semantic feature ``ctx``), head, box losses; the refinement,
+        when a later stage or an interleaved mask branch needs it; the mask hook (HTC re-samples from ``refined``)."""
+        losses = dict()
+
+        def add(i, stage_losses, weight):      # weight None: it rode in the kernel
+            for name, value in stage_losses.items():
+                weigh = weight is not None and 'loss' in name
+                losses['s{}.{}'.format(i, name)] = value * weight if weigh else value
+        for i in range(self.num_stages):
+            rc = self.train_cfg.rcnn[i]
+            lw = self.train_cfg.stage_loss_weights[i]
+            head, ext = self.bbox_head[i], self.bbox_roi_extractor[i]
+            samples = self._sample_rois_fused(proposal_list, gt_bboxes, gt_labels, samplers, rc=rc, head=head)
+            cls_score, bbox_pred = head(self._bbox_roi_feats(ext, x, samples.rois, ctx), nhwc=True,
+                                        reg_labels=samples.targets[0])
+            if getattr(head, 'fused_loss_scale', False):      # GS heads: the stage weight rides in the kernel
+                add(i, head.loss(cls_score, bbox_pred, *samples.targets, loss_scale=lw), None)
+            else:
+                add(i, head.loss(cls_score, bbox_pred, *samples.targets), lw)
+            refined = None
+            if self.interleaved or i < self.num_stages - 1:       # refine (cascade_rcnn.py:291-296), fixed shape
+                refined = self._refined_proposals(head, samples, bbox_pred, img_meta)
+            add(i, self._stage_mask_forward_train(i, x, ctx, samples, refined, gt_bboxes, gt_labels, gt_masks,
+                                                  samplers), lw)
+            if refined is not None:
+                proposal_list = refined
+        return losses
 
     def forward_train(self, img, img_meta, gt_bboxes, gt_labels, gt_bboxes_ignore=None,
                       gt_masks=None, proposals=None, samplers=None, feats=None):
@@ -959,25 +998,14 @@ class CascadeRCNN(TwoStageDetector):
             raise NotImplementedError('CascadeRCNN.forward_train runs on the GPU path only')
         x = self.extract_feat(img) if feats is None else feats
         losses = dict()
-        proposal_list = self._rpn_forward_train(x, img_meta, gt_bboxes, proposals, samplers, losses, fork_loss=True)
-        for i in range(self.num_stages):
-            rc = self.train_cfg.rcnn[i]
-            lw = self.train_cfg.stage_loss_weights[i]
-            head, ext = self.bbox_head[i], self.bbox_roi_extractor[i]
-            rois, targets = self._sample_rois_fused(proposal_list, gt_bboxes, gt_labels, samplers,
-                                                    rc=rc, head=head)
-            feats = ext(x[:ext.num_inputs], rois)
-            cls_score, bbox_pred = head(feats, nhwc=True, reg_labels=targets[0])
-            if getattr(head, 'fused_loss_scale', False):      # GS heads: the stage weight rides in the kernel
-                for name, value in head.loss(cls_score, bbox_pred, *targets, loss_scale=lw).items():
-                    losses['s{}.{}'.format(i, name)] = value
-            else:
-                for name, value in head.loss(cls_score, bbox_pred, *targets).items():
-                    losses['s{}.{}'.format(i, name)] = value * lw if 'loss' in name else value
-            if i < self.num_stages - 1:       # refine (cascade_rcnn.py:291-296), fixed shape
-                proposal_list = self._refined_proposals(head, rois, targets[0], bbox_pred, img_meta,
-                                                        rc.sampler.num)
-        self._join_rpn_loss()
+        proposal_list, rpn_fork = self._rpn_forward_train(x, img_meta, gt_bboxes, proposals, samplers, losses,
+                                                          fork_loss=True)
+        try:
+            losses.update(self._stages_forward_train(x, None, proposal_list, img_meta, gt_bboxes, gt_labels,
+                                                     gt_masks, samplers))
+        finally:
+            if rpn_fork is not None:
+                rpn_fork.join()
         return losses
 
     # -- test time: TwoStageDetector's flows with the stage loop as the box scores ------------------------
@@ -1077,20 +1105,15 @@ class HybridTaskCascade(CascadeRCNN):
             last = self.mask_head[i].res_features(mask_feats, last)
         return head.upsample_features(head.res_features(mask_feats, last))
 
-    def _htc_mask_forward_train(self, stage, x, rois, labels, gt_masks, rc, semantic_feat):
-        """htc.py:75-112 on the fixed-shape positives (the first ``int(num * pos_fraction)``
-        sampler slots of every image; ``labels > 0`` marks the real ones)."""
-        sc = rc.sampler
-        n_img = len(gt_masks)
-        max_pos = int(sc.num * sc.pos_fraction)
-        sel = (torch.arange(n_img, device=rois.device).view(-1, 1) * sc.num +
-               torch.arange(max_pos, device=rois.device).view(1, -1)).reshape(-1)
-        pos_rois = rois[sel].contiguous()
-        pos_labels = labels[sel].contiguous()
-        valid = pos_labels > 0
-        gt_inds = self._sampled_gt_inds[:, :max_pos].reshape(-1).contiguous()
-        masks = [torch.as_tensor(m).to(device=rois.device, dtype=torch.uint8).contiguous()
-                 for m in gt_masks]
+    def _stage_mask_forward_train(self, stage, x, semantic_feat, samples, refined, gt_bboxes, gt_labels, gt_masks,
+                                  samplers):
+        """htc.py:75-112 and :264-283 on the fixed-shape positives (``_mask_inputs``)."""
+        rc = self.train_cfg.rcnn[stage]
+        if self.interleaved:
+            with torch.no_grad():       # re-assigned and re-sampled from the boxes this stage's box head just refined
+                samples = self._sample_rois_fused(refined, gt_bboxes, gt_labels, samplers, rc=rc,
+                                                  head=self.bbox_head[stage])
+        pos_rois, pos_labels, valid, gt_inds, masks = self._mask_inputs(samples, gt_masks, rc.sampler)
         ext, head = self.mask_roi_extractor[stage], self.mask_head[stage]
         mask_feats = self._fused_roi_feats(ext, x, pos_rois, semantic_feat, 'mask')
         feats = self._mask_features(stage, mask_feats)
@@ -1105,46 +1128,20 @@ class HybridTaskCascade(CascadeRCNN):
             raise ValueError('HTC needs gt_masks (per image a uint8 [G, H, W] tensor)')
         x = self.extract_feat(img) if feats is None else feats
         losses = dict()
-        proposal_list = self._rpn_forward_train(x, img_meta, gt_bboxes, proposals, samplers, losses, fork_loss=True)
-        semantic_feat = None
-        if self.with_semantic:
-            if gt_semantic_seg is None:
-                raise ValueError('the semantic branch needs gt_semantic_seg [N, 1, H/8, W/8]')
-            semantic_pred, semantic_feat = self.semantic_head(x)
-            losses['loss_semantic_seg'] = self.semantic_head.loss(semantic_pred, gt_semantic_seg)
-        for i in range(self.num_stages):
-            rc = self.train_cfg.rcnn[i]
-            lw = self.train_cfg.stage_loss_weights[i]
-            head, ext = self.bbox_head[i], self.bbox_roi_extractor[i]
-            num = rc.sampler.num
-            rois, targets = self._sample_rois_fused(proposal_list, gt_bboxes, gt_labels, samplers,
-                                                    rc=rc, head=head)
-            feats = self._fused_roi_feats(ext, x, rois, semantic_feat, 'bbox')
-            cls_score, bbox_pred = head(feats, nhwc=True, reg_labels=targets[0])
-            if getattr(head, 'fused_loss_scale', False):      # GS heads: the stage weight rides in the kernel
-                for name, value in head.loss(cls_score, bbox_pred, *targets, loss_scale=lw).items():
-                    losses['s{}.{}'.format(i, name)] = value
-            else:
-                for name, value in head.loss(cls_score, bbox_pred, *targets).items():
-                    losses['s{}.{}'.format(i, name)] = value * lw if 'loss' in name else value
-            refined = None
-            if self.interleaved or i < self.num_stages - 1:
-                refined = self._refined_proposals(head, rois, targets[0], bbox_pred, img_meta, num)
-            mask_rois, mask_labels = rois, targets[0]
-            if self.interleaved:
-                # htc.py:264-283: the mask branch trains on RoIs re-assigned and re-sampled from
-                # the boxes this stage's box head just refined
-                with torch.no_grad():
-                    mask_rois, mt = self._sample_rois_fused(refined, gt_bboxes, gt_labels, samplers,
-                                                            rc=rc, head=head)
-                    mask_labels = mt[0]
-            loss_mask = self._htc_mask_forward_train(i, x, mask_rois, mask_labels, gt_masks, rc,
-                                                     semantic_feat)
-            for name, value in loss_mask.items():
-                losses['s{}.{}'.format(i, name)] = value * lw if 'loss' in name else value
-            if refined is not None:
-                proposal_list = refined
-        self._join_rpn_loss()
+        proposal_list, rpn_fork = self._rpn_forward_train(x, img_meta, gt_bboxes, proposals, samplers, losses,
+                                                          fork_loss=True)
+        try:
+            semantic_feat = None
+            if self.with_semantic:
+                if gt_semantic_seg is None:
+                    raise ValueError('the semantic branch needs gt_semantic_seg [N, 1, H/8, W/8]')
+                semantic_pred, semantic_feat = self.semantic_head(x)
+                losses['loss_semantic_seg'] = self.semantic_head.loss(semantic_pred, gt_semantic_seg)
+            losses.update(self._stages_forward_train(x, semantic_feat, proposal_list, img_meta, gt_bboxes,
+                                                     gt_labels, gt_masks, samplers))
+        finally:
+            if rpn_fork is not None:
+                rpn_fork.join()
         return losses
 
     # -- test time: the flows are TwoStageDetector's, the stage loop CascadeRCNN's ---------------------------

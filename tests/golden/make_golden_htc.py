@@ -5,8 +5,9 @@ on CPU (stubs: oracle/ref_import.py):
 * ``FusedSemanticHead`` (mmdet/models/mask_heads/fused_semantic_head.py): forward + loss +
   backward on five small FPN-shaped levels;
 * ``HTCMaskHead`` (mmdet/models/mask_heads/htc_mask_head.py): the mask-information-flow chain of
-  two heads exactly as ``HybridTaskCascade._mask_forward_train`` runs it for stage 1
-  (htc.py:98-107), then ``loss`` + backward.
+  two heads exactly as the reference's ``HybridTaskCascade._mask_forward_train`` runs it for
+  stage 1 (htc.py:98-107; this package: ``_stage_mask_forward_train`` -> ``_mask_features``),
+  then ``loss`` + backward.
 
     python tests/golden/make_golden_htc.py          # authoring container only
 

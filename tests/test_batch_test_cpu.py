@@ -146,6 +146,23 @@ def test_the_test_time_flows_are_written_once():
             assert name not in vars(cls), (cls.__name__, name)
 
 
+def test_the_training_path_is_written_once_and_keeps_nothing_on_the_module():
+    """one RoI-stage training loop (``CascadeRCNN``'s, HTC supplies hooks), one mask-input helper, one RPN part and one
+    sampler; the sampling result and the RPN-loss fork are returned, never stashed on the detector"""
+    T, C, H = detectors.TwoStageDetector, detectors.CascadeRCNN, detectors.HybridTaskCascade
+    assert H._stages_forward_train is C._stages_forward_train
+    assert '_stage_mask_forward_train' in vars(C) and '_stage_mask_forward_train' in vars(H)
+    assert H._mask_inputs is T._mask_inputs and C._mask_inputs is T._mask_inputs
+    for cls in (C, H):
+        for name in ('_rpn_forward_train', '_sample_rois_fused'):
+            assert getattr(cls, name) is getattr(T, name), (cls.__name__, name)
+    assert detectors.RoISamples._fields == ('rois', 'targets', 'gt_inds', 'valid', 'is_gt')
+    for which in ('cascade', 'htc'):
+        m = _cpu_model(which)
+        for name in ('_sampled_gt_inds', '_sampled_valid', '_sampled_is_gt', '_rpn_loss_fork'):
+            assert not hasattr(m, name), (which, name)
+
+
 def test_the_four_detector_classes_expose_the_device_tensor_cores():
     for cls in (detectors.FasterRCNN, detectors.MaskRCNN, detectors.CascadeRCNN, detectors.HybridTaskCascade):
         for name in ('simple_test_dets', 'aug_test_dets'):

@@ -241,6 +241,15 @@ def _cascade(tmp_path, depth=50):
                               test_cfg=to_config_dict(test_cfg))
 
 
+def _jittered(gt, n, n_near, W, H, seed):
+    """``n`` boxes ``[n, 4]`` on the device: random ones, the first ``n_near`` jittered copies of ``gt`` (positives)."""
+    g = torch.Generator().manual_seed(seed)
+    xy = torch.rand(n, 2, generator=g) * torch.tensor([W - 60., H - 60.])
+    b = torch.cat([xy, xy + torch.rand(n, 2, generator=g) * 100 + 4], 1)
+    b[:n_near] = gt.cpu()[torch.arange(n_near) % gt.size(0)] + torch.randn(n_near, 4, generator=g) * 2
+    return b.to(DEV)
+
+
 def test_cascade_rcnn_training_iteration_and_test(tmp_path):
     torch.manual_seed(0)
     model = _cascade(tmp_path).to(DEV)
@@ -274,7 +283,16 @@ def test_cascade_rcnn_training_iteration_and_test(tmp_path):
         assert h.fc_cls.weight.grad is not None and float(h.fc_cls.weight.grad.abs().sum()) > 0
         assert h.fc_reg.weight.grad is None
     # stage 2 / 3 re-sample from the refined boxes: the kept refined proposals exclude GT rows
-    assert model._sampled_valid.shape == (2, 512) and model._sampled_is_gt.shape == (2, 512)
+    props = [(torch.cat([_jittered(gtb[i], 1000, 40, W, H, 20 + i), torch.rand(1000, 1, device=DEV)], 1),
+              torch.ones(1000, dtype=torch.bool, device=DEV)) for i in range(2)]
+    head = model.bbox_head[0]
+    with torch.no_grad():
+        samples = model._sample_rois_fused(props, gtb, gtl, rc=model.train_cfg.rcnn[0], head=head)
+        refined = model._refined_proposals(head, samples, torch.randn(2 * 512, 4, device=DEV) * 0.1, metas)
+    kept = refined.batched[1]
+    assert kept.shape == (2, 512) and samples.valid.shape == (2, 512) and samples.is_gt.shape == (2, 512)
+    assert torch.equal(kept, samples.valid & ~samples.is_gt)
+    assert samples.is_gt.sum(1).tolist() == [10, 10]          # the GT boxes added as proposals
     model.eval()
     with torch.no_grad():
         for h in model.bbox_head:
@@ -285,6 +303,57 @@ def test_cascade_rcnn_training_iteration_and_test(tmp_path):
         ahead = model.extract_feat(img[:1])
     res2 = model(img[:1], metas[:1], return_loss=False, rescale=False, feats=ahead)
     assert all(np.array_equal(a_, b_) for a_, b_ in zip(res, res2))
+
+
+def test_sampling_records_are_independent_of_call_order(tmp_path):
+    """``_sample_rois_fused`` returns its result and keeps nothing on the module: a second sampling (HTC's interleaved
+    stage samples twice per stage) leaves the first record bit-unchanged.  Only the assign / sample / target kernels
+    run.  60 valid proposals + 3 / 5 GT boxes for ``sampler.num = 512`` slots: most slots are padding."""
+    model = _cascade(tmp_path).to(DEV)
+    W, H, counts = 480, 320, (3, 5)
+    g = torch.Generator().manual_seed(7)
+    gtb, gtl = [], []
+    for n in counts:
+        xy = torch.rand(n, 2, generator=g) * torch.tensor([W - 160., H - 160.])
+        gtb.append(torch.cat([xy, xy + torch.rand(n, 2, generator=g) * 120 + 30], 1).to(DEV))
+        gtl.append(torch.randint(1, 1231, (n,), generator=g).to(DEV))
+    valid = torch.ones(64, dtype=torch.bool, device=DEV)
+    valid[60:] = False
+
+    def proposals(seed):
+        return [(torch.cat([_jittered(gtb[i], 64, 16, W, H, seed + i), torch.rand(64, 1, device=DEV)], 1), valid)
+                for i in range(2)]
+    rc, head = model.train_cfg.rcnn[0], model.bbox_head[0]
+    assert rc.sampler.num == 512
+    first = model._sample_rois_fused(proposals(100), gtb, gtl, rc=rc, head=head)
+    flat = (first.rois,) + tuple(first.targets) + (first.gt_inds, first.valid, first.is_gt)
+    kept = [t.clone() for t in flat]
+    second = model._sample_rois_fused(proposals(200), gtb, gtl, rc=rc, head=head)
+    assert not torch.equal(second.rois, first.rois)
+    for t, k in zip(flat, kept):
+        assert torch.equal(t, k)
+    labels, lw, bt, bw = first.targets
+    assert first.valid.shape == (2, 512) and first.valid.dtype == torch.bool
+    n_valid = first.valid.sum(1).tolist()
+    assert all(0 < n_valid[i] <= 60 + counts[i] for i in range(2)), n_valid
+    pad = ~first.valid.view(-1)
+    assert int(pad.sum()) > 0
+    assert (labels[pad] == 0).all() and (lw[pad] == 0).all() and (bw[pad] == 0).all()
+    assert int((labels > 0).sum()) > sum(counts)                  # jittered proposals are positives too
+    # every GT box added as a proposal is sampled (19 / 21 positives for 128 slots).  A padding slot repeats slot 0's
+    # candidate (csrc/sampler.hip: "padding (index of slot 0, valid = 0)"), so its is_gt and gt_inds are slot 0's —
+    # a GT box or not, as the draw falls (measured: is_gt.sum over all 512 slots [3, 452] for 3 and 5 GT boxes, in
+    # the parent commit's kernel too): pos_is_gt is counted over the real slots, and the padding is pinned
+    print('is_gt.sum per image, all slots:', first.is_gt.sum(1).tolist(), 'real slots:',
+          (first.is_gt & first.valid).sum(1).tolist(), 'GT boxes:', list(counts))
+    assert (first.is_gt & first.valid).sum(1).tolist() == list(counts)
+    for i in range(2):
+        assert (first.is_gt[i][~first.valid[i]] == first.is_gt[i, 0]).all()
+        assert (first.gt_inds[i][~first.valid[i]] == first.gt_inds[i, 0]).all()
+    assert (first.gt_inds[first.is_gt] >= 0).all()
+    assert not [n for n in vars(model) if n.startswith('_sampled_')]
+    assert not hasattr(model, '_sampled_gt_inds') and not hasattr(model, '_sampled_valid') \
+        and not hasattr(model, '_sampled_is_gt')
 
 
 @pytest.mark.parametrize('agnostic', [True, False])

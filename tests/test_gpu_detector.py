@@ -367,7 +367,9 @@ def test_rcnn_fused_sampling_targets_equal_tensor_form(tmp_path):
     gen = torch.Generator(device=DEV)
     gen.manual_seed(3)
     from oracle import tensor_forms as TF
-    rois, (lab, lw, bt, bw) = model._sample_rois_fused(props, gts, labels, TF.sampler_hooks(gen))
+    rois, (lab, lw, bt, bw), gt_inds, valid, is_gt = model._sample_rois_fused(props, gts, labels,
+                                                                             TF.sampler_hooks(gen))
+    assert gt_inds is None and valid is None and is_gt is None      # a plain box detector: nobody reads them
     gen.manual_seed(3)
     samples = [TF.assign_and_sample(model, props[i][0], props[i][1], gts[i], labels[i], gen)
                for i in range(2)]

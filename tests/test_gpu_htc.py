@@ -249,6 +249,28 @@ def test_htc_training_iteration(tmp_path, selectp):
         # head 0's conv_res is never used (no previous stage): the reference leaves it without grad
         assert model.mask_head[0].conv_res.conv.weight.grad is None or \
             float(model.mask_head[0].conv_res.conv.weight.grad.abs().sum()) == 0
+    # the two arms of the stage loop that no golden covers, on the same model and inputs: the mask branch on the box
+    # branch's own samples (no re-sampling, no refinement after the last stage), and no mask information flow
+    trained = [h.fc_cls.weight for h in model.bbox_head]
+    if selectp == 0:
+        trained += [h.conv_logits.weight for h in model.mask_head] + [model.semantic_head.conv_logits.weight]
+    for arm in ('interleaved', 'mask_info_flow'):
+        assert getattr(model, arm) is True
+        setattr(model, arm, False)
+        try:
+            for p in model.parameters():
+                p.grad = None
+            arm_losses = model(img, metas, return_loss=True, gt_bboxes=gtb, gt_labels=gtl, gt_masks=gtm,
+                               gt_semantic_seg=seg)
+            assert set(arm_losses.keys()) == keys, arm
+            arm_loss, _ = train.parse_losses(arm_losses)
+            assert torch.isfinite(arm_loss) and all(
+                torch.isfinite(v).all() for vs in arm_losses.values() for v in (vs if isinstance(vs, list) else [vs]))
+            arm_loss.backward()
+            for p in trained:
+                assert p.grad is not None and torch.isfinite(p.grad).all() and float(p.grad.abs().sum()) > 0, arm
+        finally:
+            setattr(model, arm, True)
 
 
 def test_htc_simple_test_ensemble(tmp_path):
