@@ -2,7 +2,7 @@
 //
 // The reference computes fc_reg densely (mmdet/models/bbox_heads/convfc_bbox_head.py:163-165: [K, C] x [C, 4R],
 // R = 1231 classes -> 4924 columns per RoI) and its consumers then gather 4 of them: the box loss reads slot
-// (r, labels[r]) of the positives (gs_bbox_head_with0.py:173-185; csrc/bbox_loss.hip, csrc/gs_loss.hip) and the
+// (r, labels[r]) of the positives (gs_bbox_head_with0.py:173-185; csrc/bbox_loss.hip, csrc/gs_head.hip) and the
 // cascade hand-over reads the same slot of every row (bbox_head.py:210-239; csrc/det_targets.hip).  While fc_reg is
 // frozen (no gradient asks for the other columns) the gather can move in front of the product:
 //     y[r, j] = x[r, :] . W[4 l + j, :] + b[4 l + j],   l = labels[r],  j = 0..3

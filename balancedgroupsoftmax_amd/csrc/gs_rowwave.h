@@ -94,7 +94,7 @@ __device__ __forceinline__ void bin_softmax_inplace(float* __restrict__ seg, int
 // computed there and the gradient is written back ONCE.  Reads past the end of the bin stay
 // inside the row buffer (the caller pads it by 64*kSweep floats) and are masked out.
 // Returns the row's loss term  coef * (logsumexp - z[tgt]),  formed as  logf(S) - (zt - m)  here and at every other
-// site (gs_loss.hip): zt - m is exact or nearly so (both lie in the bin, m >= zt), so the term carries the error of
+// site (gs_loss.hip, gs_head.hip): zt - m is exact or nearly so (both lie in the bin, m >= zt), so the term carries the error of
 // logf(S) alone and the loss is shift-invariant like the reference's (zt - m) - log(S); (m + logf(S)) - zt would round
 // the sum to half an ulp of m — 3e-5 per row at a common offset of 1000, whatever the loss.
 template <bool WRITE_GRAD>

@@ -56,7 +56,7 @@ int bgs_selftest_mfma_peak_bf16(int blocks, int iters, int random_operands, floa
 #define BGS_CENSUS_FAMILIES 20
 int bgs_launch_census(int family, int reset);
 
-/* ---- fused GroupSoftmax head (csrc/gs_loss.hip) ---------------------------------------------------
+/* ---- fused GroupSoftmax head (csrc/gs_head.hip) ---------------------------------------------------
  * bgs_gs_head_debug_timestamps: buf != NULL (device, [2048][8] uint64) makes every later launch record 8
  *   shader-clock marks per workgroup (tools/gs_phase_times.py); NULL (default) switches it off.
  * bgs_gs_head_tuning: rows per workgroup (0 = default).

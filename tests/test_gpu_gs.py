@@ -642,6 +642,45 @@ def test_fused_head_kernel_equals_prepare_plus_loss(name, head_variant):
         np.testing.assert_array_equal(z1.grad.cpu().numpy(), z0.grad.cpu().numpy())
 
 
+def test_fused_head_kernel_rows_wider_than_two_16_byte_pieces_per_thread():
+    """The tail of the head kernels' row staging (columns beyond 2 x 256 x VEC) in its 16-byte form, which needs
+    W > 2048: a 2047-class table gives W = 2052 (0 mod 4, four columns past 2048) with every foreground bin wider than
+    the 384-column register sweep.  Variants 1 - 5, N = 3 and N = 65 (the second with padding rows), against
+    ``gs_prepare`` + ``group_softmax_loss`` with the same seed and draw counter: bitwise."""
+    from balancedgroupsoftmax_amd import capi
+    lib = capi.load()
+    classes = 2047
+    l2b, ps, _ = gs_tables.build_group_tables(gs_tables.synthetic_instance_counts(classes, seed=0))
+    W = int(ps[:, 1].sum())
+    assert ps.tolist() == [[0, 2], [2, 481], [483, 487], [970, 436], [1406, 646]]
+    assert W == 2052 and W % 4 == 0 and W > 2 * 256 * 4
+    assert all(int(n) > 384 for n in ps[1:, 1])
+    l2b_t = dev(l2b)
+    draw = torch.full((1,), 7, dtype=torch.int64, device=DEV)
+    try:
+        for n in (3, 65):
+            batch = gs_oracle.make_roi_batch(n, W, classes, seed=300 + n)
+            labels = dev(batch['labels'])
+            rw_t = dev((np.arange(n) % 5 != 3).astype(np.float32)) if n == 65 else None
+            bl, w, avg = BF.gs_prepare(labels, l2b_t, 8.0, seed=4242, seed_offset=draw, row_weights=rw_t)
+            z0 = dev(batch['logits']).requires_grad_(True)
+            ref = BF.group_softmax_loss(z0, bl, ps, w, avg)
+            ref.sum().backward()
+            for variant in (1, 2, 3, 4, 5):
+                lib.bgs_gs_head_variant(variant)
+                z1 = dev(batch['logits']).requires_grad_(True)
+                got, avg1, bl1, w1 = BF.gs_head_loss_fused(z1, labels, l2b_t, ps, 8.0, 4242, seed_offset=draw,
+                                                           row_weights=rw_t, debug=True)
+                got.sum().backward()
+                np.testing.assert_array_equal(bl1.cpu().numpy(), bl.cpu().numpy())
+                np.testing.assert_array_equal(w1.cpu().numpy(), w.cpu().numpy())
+                np.testing.assert_array_equal(avg1.detach().cpu().numpy(), avg.cpu().numpy())
+                np.testing.assert_array_equal(got.detach().cpu().numpy(), ref.detach().cpu().numpy())
+                np.testing.assert_array_equal(z1.grad.cpu().numpy(), z0.grad.cpu().numpy())
+    finally:
+        lib.bgs_gs_head_variant(-1)
+
+
 def test_fused_head_kernel_large_batch_and_forward_only(head_variant):
     """N = 4096 (the fused kernel's limit; each workgroup owns two rows) and the forward-only
     launch; exact sample counts per bin."""
