@@ -561,3 +561,410 @@ extern "C" int bgs_sample_rois_ex(const int* const* host_assigned, const int* ho
                      n_exp_pos, seed, draw_counter, inds, is_pos, valid);
   BGS_RETURN_LAUNCH_STATUS();
 }
+
+// ---------------------------------------------------------------------------------------------
+// Balanced RoI samplers of Libra R-CNN (CombinedSampler = InstanceBalancedPosSampler +
+// IoUBalancedNegSampler; instance_balanced_pos_sampler.py:9-41, iou_balanced_neg_sampler.py:44-133,
+// base_sampler.py:60-75) for a batch in ONE launch, one workgroup per image.  The reference builds numpy
+// sets and loops over ground truths and intervals on the host, with a .cpu() per step.
+//
+// Every candidate belongs to a GROUP (positives: its ground truth; negatives: its IoU interval, "IoU set
+// outside every interval", the floor set, or neither) and every group has an integer QUOTA computed from
+// the class counts exactly as the reference computes it.  A uniform k-subset of a group = its k members
+// with the smallest keys of a bijective mixer (no ties), so one in-LDS sort of (group, key, index)
+// composites makes every group contiguous and "rank inside the group < quota" the first draw.  The fills
+// (positives short of / over n_exp, the IoU set short of its quota, the final fill from all remaining
+// negatives) are two more sorts with keys of their own, each run only when its fill is non-empty.
+// The result is compacted in candidate order (the reference's unique() sorts it as well): no atomics on
+// the result, the same (seed, counter) gives the same bits.
+namespace {
+
+constexpr int kSubBits = 14;                 // group = class : 2 | sub : 14
+constexpr int kMaxBins = 1024;
+constexpr int kCandPerThread = kMaxCand / kThreadsS;
+constexpr unsigned kSelPos = 1, kSelNeg = 2;
+constexpr int kGrpNone = 0xffff;             // ignored candidates (assigned < 0): never sorted
+
+struct BalancedTable {
+  CandTable c;
+  const float* max_overlaps[kMaxImgsS];      // [count] float32 (1.0 on the leading GT rows)
+};
+
+struct BalancedCfg {
+  int num, n_exp_pos, pos_mode, neg_mode, num_bins;
+  double neg_pos_ub, floor_fraction;
+  float floor_thr;
+};
+
+__device__ __forceinline__ uint32_t stage_offset(uint64_t seed, const long long* draw, int n, int stage) {
+  const uint64_t d = draw ? (uint64_t)draw[0] : 0ull;
+  uint64_t h = seed + 0x9E3779B97F4A7C15ull * (d + 1ull) + 0xD1B54A32D192ED03ull * ((uint64_t)n + 1ull) +
+               0xA24BAED4963EE407ull * (uint64_t)stage;
+  h ^= h >> 30; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 27;
+  return (uint32_t)(h >> 16);
+}
+
+__device__ __forceinline__ unsigned long long composite(int grp, uint32_t key, int idx) {
+  return ((unsigned long long)grp << 44) | ((unsigned long long)key << 12) | (unsigned long long)idx;
+}
+
+// floor_thr + b * iou_interval in float32 as numpy evaluates it (sample_via_interval:51-52): the product is
+// rounded before the sum, so no fused multiply-add
+__device__ __forceinline__ float interval_bound(float thr, int b, float interval) {
+#pragma clang fp contract(off)
+  const float p = (float)b * interval;
+  return thr + p;
+}
+
+// ascending in-LDS bitonic sort of buf[0, P), P a power of two >= 64; all kThreadsS threads call it
+__device__ void bitonic_sort_lds(unsigned long long* buf, int P) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int j = tid; j < P / 2; j += kThreadsS) {
+        const int lo = 2 * j - (j & (stride - 1));
+        const int hi = lo + stride;
+        const bool asc = ((lo & size) == 0);
+        const unsigned long long a = buf[lo], b = buf[hi];
+        if ((a > b) == asc) {
+          buf[lo] = b;
+          buf[hi] = a;
+        }
+      }
+      bgs::bitonic_stage_sync(size, stride);
+    }
+  }
+  __syncthreads();
+}
+
+// first position of sorted buf[0, P) whose composite is >= v
+__device__ __forceinline__ int lower_bound_lds(const unsigned long long* buf, int P, unsigned long long v) {
+  int lo = 0, hi = P;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (buf[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// workgroup sums of up to four ints per thread -> every thread; s_red: [4 * kThreadsS / 64]
+__device__ void block_sum4(int v[4], int* s_red) {
+  const int tid = threadIdx.x, wave = tid >> 6;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = bgs::wave_sum_i(v[k]);
+  __syncthreads();                            // s_red may still be read from the previous call
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s_red[k * (kThreadsS / 64) + wave] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int s = 0;
+    for (int w = 0; w < kThreadsS / 64; ++w) s += s_red[k * (kThreadsS / 64) + w];
+    v[k] = s;
+  }
+}
+
+__global__ __launch_bounds__(kThreadsS) void sample_rois_balanced_kernel(
+    BalancedTable T, BalancedCfg C, uint64_t seed, const long long* __restrict__ draw,
+    long long* __restrict__ inds, uint8_t* __restrict__ is_pos, uint8_t* __restrict__ valid) {
+  __shared__ unsigned long long buf[kMaxCand];
+  __shared__ unsigned short s_grp[kMaxCand];
+  __shared__ uint8_t s_sel[kMaxCand];
+  __shared__ int s_red[4 * (kThreadsS / 64)];
+  __shared__ float s_max[kThreadsS / 64];
+  __shared__ int s_first;
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int A = T.c.count[n];
+  const int* assigned = T.c.assigned[n];
+  const float* mo = T.max_overlaps[n];
+  const int nb = C.num_bins;
+  const float thr = C.floor_thr;
+  int P = 64;
+  while (P < A) P <<= 1;
+
+  // ---- pass 0: class counts, the IoU / floor sets of the negatives, max_iou over ALL candidates
+  int cnt[4] = {0, 0, 0, 0};                  // pos, neg, neg & IoU set, neg & floor set
+  float vmax = -INFINITY;
+  for (int i = tid; i < A; i += kThreadsS) {
+    const int a = assigned[i];
+    const float o = mo[i];
+    vmax = fmaxf(vmax, o);
+    cnt[0] += a > 0;
+    if (a == 0) {
+      cnt[1] += 1;
+      // iou_balanced_neg_sampler.py:86-100
+      const bool in_iou = thr > 0.f ? o >= thr : o > thr;
+      const bool in_floor = thr > 0.f ? (o >= 0.f && o < thr) : (thr == 0.f ? o == 0.f : false);
+      cnt[2] += in_iou;
+      cnt[3] += in_floor;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
+  if (lane == 0) s_max[wave] = vmax;
+  if (tid == 0) s_first = 0;
+  block_sum4(cnt, s_red);                     // (its barriers also publish s_max)
+  float max_iou = s_max[0];
+  for (int w = 1; w < kThreadsS / 64; ++w) max_iou = fmaxf(max_iou, s_max[w]);
+  const int n_pos = cnt[0], n_neg = cnt[1], n_iou = cnt[2], n_floor = cnt[3];
+
+  // ---- the reference's integers (base_sampler.py:60-72, iou_balanced_neg_sampler.py:104-117)
+  const int n_exp = C.n_exp_pos;
+  const int k_pos = min(n_exp, n_pos);
+  int n_exp_neg = C.num - k_pos;
+  if (C.neg_pos_ub >= 0.0) {
+    const int ub = (int)(C.neg_pos_ub * (double)max(k_pos, 1));
+    n_exp_neg = min(n_exp_neg, ub);
+  }
+  const int k_neg = max(0, min(n_exp_neg, n_neg));
+  const bool pos_all = n_pos <= n_exp, neg_all = n_neg <= n_exp_neg;
+  const bool neg_bal = C.neg_mode == 1 && !neg_all;
+  int n_iou_exp = 0, q_bin = 0, q_floor = 0;
+  bool iou_all = false;
+  if (neg_bal) {
+    n_iou_exp = (int)((double)n_exp_neg * (1.0 - C.floor_fraction));
+    iou_all = n_iou <= n_iou_exp;
+    q_bin = nb >= 2 ? n_iou_exp / nb : n_iou_exp;
+    q_floor = n_exp_neg - (iou_all ? n_iou : n_iou_exp);
+  }
+  const float interval = (max_iou - thr) / (float)nb;      // float32, sample_via_interval:45-46
+
+  // ---- pass 1: groups and the first sort.  sub of a positive: its gt (instance-balanced) or 0;
+  // of a negative: interval i < nb, nb = IoU set outside every interval, nb + 1 = floor set, nb + 2 = neither
+  const uint32_t off1 = stage_offset(seed, draw, n, 1);
+  for (int i = tid; i < P; i += kThreadsS) {
+    unsigned long long comp = ~0ull;
+    int grp = kGrpNone;
+    if (i < A) {
+      const int a = assigned[i];
+      if (a > 0) {
+        grp = C.pos_mode == 1 ? min(a - 1, (1 << kSubBits) - 1) : 0;
+      } else if (a == 0) {
+        int sub = 0;
+        if (neg_bal) {
+          const float o = mo[i];
+          const bool in_iou = thr > 0.f ? o >= thr : o > thr;
+          const bool in_floor = thr > 0.f ? (o >= 0.f && o < thr) : (thr == 0.f ? o == 0.f : false);
+          if (in_iou) {
+            sub = nb >= 2 ? nb : 0;
+            for (int b = 0; nb >= 2 && b < nb; ++b) {
+              const float start = interval_bound(thr, b, interval);
+              const float end = interval_bound(thr, b + 1, interval);
+              if (o >= start && o < end) {
+                sub = b;
+                break;
+              }
+            }
+          } else {
+            sub = in_floor ? nb + 1 : nb + 2;
+          }
+        }
+        grp = (1 << kSubBits) | sub;
+      }
+      if (grp != kGrpNone) comp = composite(grp, mix32((uint32_t)i + off1), i);
+      s_grp[i] = (unsigned short)grp;
+      s_sel[i] = 0;
+    }
+    buf[i] = comp;
+  }
+  bitonic_sort_lds(buf, P);
+
+  // distinct assigned gts (instance_balanced_pos_sampler.py:16-18; Python's round is half-to-even, as rint)
+  int num_per_gt = n_exp;
+  if (!pos_all && C.pos_mode == 1) {
+    int c[4] = {0, 0, 0, 0};
+    for (int j = tid; j < n_pos; j += kThreadsS) c[0] += j == 0 || (buf[j] >> 44) != (buf[j - 1] >> 44);
+    block_sum4(c, s_red);
+    num_per_gt = (int)(rint((double)n_exp / (double)c[0]) + 1.0);
+  }
+  // first draw: rank inside the group < quota
+  int got[4] = {0, 0, 0, 0};                  // chosen positives, chosen of the IoU set
+  for (int j = tid; j < n_pos + n_neg; j += kThreadsS) {
+    const unsigned long long comp = buf[j];
+    const int grp = (int)(comp >> 44), sub = grp & ((1 << kSubBits) - 1);
+    const int rank = j - lower_bound_lds(buf, P, (unsigned long long)grp << 44);
+    int quota;
+    if (j < n_pos) quota = pos_all ? kMaxCand : num_per_gt;
+    else if (!neg_bal) quota = k_neg;
+    else if (sub < nb) quota = iou_all ? kMaxCand : q_bin;
+    else if (sub == nb) quota = iou_all ? kMaxCand : 0;
+    else quota = sub == nb + 1 ? q_floor : 0;
+    if (rank < quota) {
+      s_sel[comp & 0xfffull] = j < n_pos ? kSelPos : kSelNeg;
+      got[0] += j < n_pos;
+      got[1] += j >= n_pos && neg_bal && sub <= nb;
+    }
+  }
+  block_sum4(got, s_red);
+  const int u_pos = got[0], c_iou = got[1];
+
+  // ---- second sort: the positives' fill (or cut) and the IoU set's fill, keys of their own
+  const bool pos_fill = !pos_all && u_pos < n_exp, pos_cut = !pos_all && u_pos > n_exp;
+  const bool iou_fill = neg_bal && !iou_all && c_iou < n_iou_exp;
+  if (pos_fill || pos_cut || iou_fill) {
+    const uint32_t off2 = stage_offset(seed, draw, n, 2);
+    for (int i = tid; i < P; i += kThreadsS) {
+      unsigned long long comp = ~0ull;
+      if (i < A) {
+        const int grp = s_grp[i], sel = s_sel[i];
+        if (grp != kGrpNone) {
+          const bool pos = (grp >> kSubBits) == 0;
+          const int sub = grp & ((1 << kSubBits) - 1);
+          int cls = -1;
+          if (pos && ((pos_fill && !sel) || (pos_cut && sel))) cls = 0;
+          if (!pos && iou_fill && !sel && sub <= nb) cls = 1;
+          if (cls >= 0) comp = composite(cls << kSubBits, mix32((uint32_t)i + off2), i);
+        }
+      }
+      buf[i] = comp;
+    }
+    bitonic_sort_lds(buf, P);
+    const int start1 = lower_bound_lds(buf, P, 1ull << (44 + kSubBits));
+    const int end1 = lower_bound_lds(buf, P, 2ull << (44 + kSubBits));
+    for (int j = tid; j < end1; j += kThreadsS) {
+      const int idx = (int)(buf[j] & 0xfffull);
+      if (j < start1) {
+        if (pos_fill && j < n_exp - u_pos) s_sel[idx] = kSelPos;
+        if (pos_cut && j >= n_exp) s_sel[idx] = 0;
+      } else if (j - start1 < n_iou_exp - c_iou) {
+        s_sel[idx] = kSelNeg;
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- third sort: the final fill from all remaining negatives (iou_balanced_neg_sampler.py:125-130)
+  const int n_fill = neg_bal ? n_exp_neg - (iou_all ? n_iou : n_iou_exp) - min(n_floor, q_floor) : 0;
+  if (n_fill > 0) {
+    const uint32_t off3 = stage_offset(seed, draw, n, 3);
+    for (int i = tid; i < P; i += kThreadsS) {
+      unsigned long long comp = ~0ull;
+      if (i < A) {
+        const int grp = s_grp[i];
+        if (grp != kGrpNone && (grp >> kSubBits) == 1 && !s_sel[i])
+          comp = composite(0, mix32((uint32_t)i + off3), i);
+      }
+      buf[i] = comp;
+    }
+    bitonic_sort_lds(buf, P);
+    for (int j = tid; j < min(n_fill, P); j += kThreadsS)
+      if (buf[j] != ~0ull) s_sel[buf[j] & 0xfffull] = kSelNeg;
+    __syncthreads();
+  }
+
+  // ---- compaction in candidate order: positives, negatives, padding (index of slot 0, valid = 0)
+  int sel[kCandPerThread], mine = 0;          // low half: positives, high half: negatives
+#pragma unroll
+  for (int k = 0; k < kCandPerThread; ++k) {
+    const int i = tid * kCandPerThread + k;
+    sel[k] = i < A ? s_sel[i] : 0;
+    mine += (sel[k] == kSelPos) + ((sel[k] == kSelNeg) << 16);
+  }
+  int incl = mine;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int t = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += t;
+  }
+  __syncthreads();
+  if (lane == 63) s_red[wave] = incl;
+  __syncthreads();
+  int base = 0, total = 0;
+  for (int w = 0; w < kThreadsS / 64; ++w) {
+    if (w < wave) base += s_red[w];
+    total += s_red[w];
+  }
+  const int tot_pos = total & 0xffff, tot_neg = total >> 16;
+  int at = base + incl - mine;
+  int at_pos = at & 0xffff, at_neg = tot_pos + (at >> 16);
+  long long* o_inds = inds + (size_t)n * C.num;
+  uint8_t* o_pos = is_pos + (size_t)n * C.num;
+  uint8_t* o_valid = valid + (size_t)n * C.num;
+  int* o_gt = T.c.gt_ind ? T.c.gt_ind + (size_t)n * C.num : nullptr;
+  uint8_t* o_isgt = T.c.is_gt ? T.c.is_gt + (size_t)n * C.num : nullptr;
+#pragma unroll
+  for (int k = 0; k < kCandPerThread; ++k) {
+    if (!sel[k]) continue;
+    const int i = tid * kCandPerThread + k;
+    const int slot = sel[k] == kSelPos ? at_pos++ : at_neg++;
+    if (slot >= C.num) continue;              // (the quotas sum to <= num)
+    if (slot == 0) s_first = i;
+    o_inds[slot] = i;
+    o_pos[slot] = sel[k] == kSelPos;
+    o_valid[slot] = 1;
+    if (o_gt) o_gt[slot] = assigned[i] - 1;
+    if (o_isgt) o_isgt[slot] = i < T.c.n_gt[n] ? 1 : 0;
+  }
+  __syncthreads();
+  const int first = s_first;
+  for (int j = min(tot_pos + tot_neg, C.num) + tid; j < C.num; j += kThreadsS) {
+    o_inds[j] = first;
+    o_pos[j] = 0;
+    o_valid[j] = 0;
+    if (o_gt) o_gt[j] = assigned[first] - 1;
+    if (o_isgt) o_isgt[j] = first < T.c.n_gt[n] ? 1 : 0;
+  }
+}
+
+}  // namespace
+
+extern "C" int bgs_sample_rois_balanced_ex(const int* const* host_assigned, const float* const* host_max_overlaps,
+                                           const int* host_counts, const int* host_gt_counts, int N, int num,
+                                           double pos_fraction, double neg_pos_ub, int pos_mode, int neg_mode,
+                                           double floor_thr, double floor_fraction, int num_bins, uint64_t seed,
+                                           const long long* draw_counter, long long* inds, uint8_t* is_pos,
+                                           uint8_t* valid, int* gt_ind, uint8_t* is_gt, bgs_stream_t stream) {
+  if (N < 0 || N > kMaxImgsS || num <= 0 || !(pos_fraction >= 0.0 && pos_fraction <= 1.0))
+    return BGS_ERR_INVALID_ARG;
+  if ((pos_mode != 0 && pos_mode != 1) || (neg_mode != 0 && neg_mode != 1)) return BGS_ERR_INVALID_ARG;
+  // iou_balanced_neg_sampler.py:36-38
+  if (!(floor_thr >= 0.0 || floor_thr == -1.0) || !(floor_fraction >= 0.0 && floor_fraction <= 1.0) ||
+      num_bins < 1 || num_bins > kMaxBins)
+    return BGS_ERR_INVALID_ARG;
+  if (N == 0) return BGS_OK;
+  if (!host_assigned || !host_max_overlaps || !host_counts || !inds || !is_pos || !valid)
+    return BGS_ERR_INVALID_ARG;
+  BalancedTable T;
+  for (int i = 0; i < kMaxImgsS; ++i) {
+    T.c.assigned[i] = nullptr;
+    T.c.count[i] = 0;
+    T.c.n_gt[i] = 0;
+    T.max_overlaps[i] = nullptr;
+  }
+  T.c.gt_ind = gt_ind;
+  T.c.is_gt = is_gt;
+  for (int i = 0; i < N; ++i) {
+    if (host_counts[i] <= 0 || host_counts[i] > kMaxCand || !host_assigned[i] || !host_max_overlaps[i])
+      return BGS_ERR_UNSUPPORTED;
+    T.c.assigned[i] = host_assigned[i];
+    T.c.count[i] = host_counts[i];
+    T.c.n_gt[i] = host_gt_counts ? host_gt_counts[i] : 0;
+    T.max_overlaps[i] = host_max_overlaps[i];
+  }
+  BalancedCfg C;
+  C.num = num;
+  C.n_exp_pos = (int)((double)num * pos_fraction);
+  C.pos_mode = pos_mode;
+  C.neg_mode = neg_mode;
+  C.num_bins = num_bins;
+  C.neg_pos_ub = neg_pos_ub;
+  C.floor_fraction = floor_fraction;
+  C.floor_thr = (float)floor_thr;
+  hipLaunchKernelGGL(sample_rois_balanced_kernel, dim3(N), dim3(kThreadsS), 0, (hipStream_t)stream, T, C,
+                     seed, draw_counter, inds, is_pos, valid);
+  BGS_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int bgs_sample_rois_balanced(const int* const* host_assigned, const float* const* host_max_overlaps,
+                                        const int* host_counts, const int* host_gt_counts, int N, int num,
+                                        double pos_fraction, double neg_pos_ub, int pos_mode, int neg_mode,
+                                        double floor_thr, double floor_fraction, int num_bins, uint64_t seed,
+                                        const long long* draw_counter, long long* inds, uint8_t* is_pos,
+                                        uint8_t* valid, bgs_stream_t stream) {
+  return bgs_sample_rois_balanced_ex(host_assigned, host_max_overlaps, host_counts, host_gt_counts, N, num,
+                                     pos_fraction, neg_pos_ub, pos_mode, neg_mode, floor_thr, floor_fraction,
+                                     num_bins, seed, draw_counter, inds, is_pos, valid, nullptr, nullptr, stream);
+}

@@ -51,6 +51,46 @@ def _gt_index_row(G, device):
     return t
 
 
+_POS_SAMPLERS = {'RandomSampler': 0, 'InstanceBalancedPosSampler': 1}
+_NEG_SAMPLERS = {'RandomSampler': 0, 'IoUBalancedNegSampler': 1}
+
+
+def roi_sampler_plan(sc):
+    """``train_cfg.rcnn.sampler`` -> ``None`` for the uniform ``RandomSampler`` (``bgs_sample_rois``), or the keyword
+    arguments of ``functional.sample_rois_balanced`` for the Libra R-CNN samplers: ``CombinedSampler`` over
+    ``RandomSampler`` / ``InstanceBalancedPosSampler`` / ``IoUBalancedNegSampler``
+    (mmdet/core/bbox/samplers/combined_sampler.py:5-16), or one of the two balanced classes as the whole sampler (both
+    subclass ``RandomSampler`` and inherit its other half).  Every other name is refused by name."""
+    kind = sc.get('type', 'RandomSampler')
+    if kind == 'RandomSampler':
+        return None
+    if kind == 'CombinedSampler':
+        if sc.get('pos_sampler') is None or sc.get('neg_sampler') is None:
+            raise ValueError('CombinedSampler needs a pos_sampler and a neg_sampler')
+        pos, neg = sc.get('pos_sampler'), sc.get('neg_sampler')
+    elif kind == 'InstanceBalancedPosSampler':
+        pos, neg = sc, dict(type='RandomSampler')
+    elif kind == 'IoUBalancedNegSampler':
+        pos, neg = dict(type='RandomSampler'), sc
+    else:
+        raise NotImplementedError('train_cfg.rcnn.sampler.type = %r: the RoI stage samples with RandomSampler, '
+                                  'CombinedSampler, InstanceBalancedPosSampler or IoUBalancedNegSampler' % (kind,))
+    pk, nk = pos.get('type', None), neg.get('type', None)
+    if pk not in _POS_SAMPLERS:
+        raise NotImplementedError('CombinedSampler.pos_sampler.type = %r: RandomSampler or '
+                                  'InstanceBalancedPosSampler' % (pk,))
+    if nk not in _NEG_SAMPLERS:
+        raise NotImplementedError('CombinedSampler.neg_sampler.type = %r: RandomSampler or '
+                                  'IoUBalancedNegSampler' % (nk,))
+    floor_thr, floor_fraction, num_bins = neg.get('floor_thr', -1), neg.get('floor_fraction', 0), neg.get('num_bins', 3)
+    # iou_balanced_neg_sampler.py:36-38
+    assert floor_thr >= 0 or floor_thr == -1
+    assert 0 <= floor_fraction <= 1
+    assert num_bins >= 1
+    return dict(pos_mode=_POS_SAMPLERS[pk], neg_mode=_NEG_SAMPLERS[nk], neg_pos_ub=sc.get('neg_pos_ub', -1),
+                floor_thr=floor_thr, floor_fraction=floor_fraction, num_bins=num_bins)
+
+
 @DETECTORS.register_module
 class TwoStageDetector(nn.Module):
 
@@ -161,21 +201,36 @@ class TwoStageDetector(nn.Module):
         offs = [0]
         for g in gt_bboxes:
             offs.append(offs[-1] + int(g.size(0)))
-        assigned = BF.iou_assign(props, gt_cat, offs, ac.pos_iou_thr, ac.neg_iou_thr,
-                                 ac.get('min_pos_iou', 0.0), valid=pvalid, shared_boxes=False)
-        add_gt = sc.get('add_gt_as_proposals', True)
         rcnn_hook = samplers.get('rcnn') if samplers else None
+        plan = roi_sampler_plan(sc)                 # None: RandomSampler; names outside the RoI stage's raise here
+        max_ov = None
+        if plan is not None and rcnn_hook is None:  # the IoU-balanced draw reads AssignResult.max_overlaps
+            assigned, max_ov = BF.iou_assign(props, gt_cat, offs, ac.pos_iou_thr, ac.neg_iou_thr,
+                                             ac.get('min_pos_iou', 0.0), valid=pvalid, shared_boxes=False,
+                                             return_max_overlaps=True)
+        else:
+            assigned = BF.iou_assign(props, gt_cat, offs, ac.pos_iou_thr, ac.neg_iou_thr,
+                                     ac.get('min_pos_iou', 0.0), valid=pvalid, shared_boxes=False)
+        add_gt = sc.get('add_gt_as_proposals', True)
         # only the mask branch and the cascade refinement read gt_inds / valid / is_gt: the plain box detectors
         # launch bgs_sample_rois (not _ex), and under the test hook skip ~10 small launches
         need_extra = self.with_mask or isinstance(self.bbox_head, nn.ModuleList)
         gt_inds = valid = is_gt = None
-        boxes_l, assigned_l, inds_l, valid_l = [], [], [], []
+        boxes_l, assigned_l, inds_l, valid_l, max_ov_l = [], [], [], [], []
+        if max_ov is not None and add_gt:
+            # one fill and one copy for the batch instead of a fill and a cat per image: image i's overlaps are the
+            # last G_i + P entries of row i, ones in front of the proposals'
+            g_max = max(int(g.size(0)) for g in gt_bboxes)
+            max_ov_gt = max_ov.new_ones((N, g_max + max_ov.size(1)))
+            max_ov_gt[:, g_max:] = max_ov
         for i in range(N):
             b, a = props[i, :, :4], assigned[i]
             if add_gt:      # base_sampler.py:49-53 + AssignResult.add_gt_
                 G = gt_bboxes[i].size(0)
                 b = torch.cat([gt_bboxes[i][:, :4].float(), b], 0)
                 a = torch.cat([_gt_index_row(G, a.device), a])
+            if max_ov is not None:      # add_gt_: the GT rows overlap themselves fully
+                max_ov_l.append(max_ov_gt[i, g_max - G:] if add_gt else max_ov[i])
             boxes_l.append(b.contiguous())
             assigned_l.append(a.contiguous())
             if rcnn_hook is not None:      # test hook: caller-supplied draw
@@ -187,9 +242,13 @@ class TwoStageDetector(nn.Module):
                 raise NotImplementedError('bgs_sample_rois sorts <= 4096 candidates per image in LDS '
                                           '(rpn_proposal.max_num + GT boxes)')
             # one launch for the batch (csrc/sampler.hip: sort of (class, random key) composites)
-            res = BF.sample_rois(assigned_l, sc.num, sc.pos_fraction,
-                                 gt_counts=[int(g.size(0)) if add_gt else 0 for g in gt_bboxes]
-                                 if need_extra else None)
+            gt_counts = [int(g.size(0)) if add_gt else 0 for g in gt_bboxes]
+            if plan is None:
+                res = BF.sample_rois(assigned_l, sc.num, sc.pos_fraction,
+                                     gt_counts=gt_counts if need_extra else None)
+            else:       # the Libra R-CNN samplers: sorts of (group, random key) composites, quotas per group
+                res = BF.sample_rois_balanced(assigned_l, max_ov_l, sc.num, sc.pos_fraction, gt_counts,
+                                              extra=need_extra, **plan)
             inds_all, valid_all = res[0], res[2].view(torch.bool)
             inds_l = [inds_all[i] for i in range(N)]
             valid_l = [valid_all[i] for i in range(N)]

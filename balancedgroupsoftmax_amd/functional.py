@@ -2822,6 +2822,47 @@ def sample_rois(assigned_list, num, pos_fraction, gt_counts=None):
     return inds, is_pos, valid
 
 
+def sample_rois_balanced(assigned_list, max_overlaps_list, num, pos_fraction, gt_counts, neg_pos_ub=-1,
+                         pos_mode=1, neg_mode=1, floor_thr=-1, floor_fraction=0, num_bins=3, extra=False,
+                         seed=None, draw_counter=None):
+    """The balanced RoI samplers of Libra R-CNN for a batch in one launch (``bgs_sample_rois_balanced``): per image
+    ``assigned [A_n]`` int32 and ``max_overlaps [A_n]`` float32 (candidates = ``gt_counts[n]`` GT boxes with overlap
+    1.0, then the proposals; ``A_n <= 4096``) -> ``inds [N, num]`` int64 (positives first), ``is_pos``, ``valid``
+    ``[N, num]`` uint8, and with ``extra`` also ``gt_ind`` int32 and ``is_gt`` uint8 as ``sample_rois`` returns them.
+
+    ``pos_mode`` 0 = RandomSampler, 1 = InstanceBalancedPosSampler; ``neg_mode`` 0 = RandomSampler, 1 =
+    IoUBalancedNegSampler with ``floor_thr`` / ``floor_fraction`` / ``num_bins``.  ``seed`` / ``draw_counter`` (device
+    int64 ``[1]``): a caller's own draw instead of the per-device counter; the same pair returns the same bits."""
+    _require_cuda(*assigned_list, *max_overlaps_list)
+    lib = capi.load()
+    N = len(assigned_list)
+    assert len(max_overlaps_list) == N and len(gt_counts) == N
+    dev = assigned_list[0].device
+    for a, o in zip(assigned_list, max_overlaps_list):
+        assert a.dtype == torch.int32 and a.is_contiguous() and a.dim() == 1
+        assert o.dtype == torch.float32 and o.is_contiguous() and o.shape == a.shape
+    ctr = _draw_counter(dev, 'rois_balanced') if draw_counter is None else draw_counter
+    if seed is None:
+        seed = (torch.initial_seed() * 0x9E3779B1 + 0x3C6EF372) & 0xFFFFFFFFFFFFFFFF
+    inds = torch.empty((N, num), dtype=torch.int64, device=dev)
+    is_pos = torch.empty((N, num), dtype=torch.uint8, device=dev)
+    valid = torch.empty((N, num), dtype=torch.uint8, device=dev)
+    args = (_c_ptr_array(assigned_list), _c_ptr_array(max_overlaps_list),
+            _c_int_array([int(a.numel()) for a in assigned_list]), _c_int_array(gt_counts), N, int(num),
+            float(pos_fraction), float(neg_pos_ub), int(pos_mode), int(neg_mode), float(floor_thr),
+            float(floor_fraction), int(num_bins), int(seed), capi.ptr(ctr), capi.ptr(inds), capi.ptr(is_pos),
+            capi.ptr(valid))
+    if extra:
+        gt_ind = torch.empty((N, num), dtype=torch.int32, device=dev)
+        is_gt = torch.empty((N, num), dtype=torch.uint8, device=dev)
+        rc = lib.bgs_sample_rois_balanced_ex(*args, capi.ptr(gt_ind), capi.ptr(is_gt), capi.current_stream(dev))
+        capi.check('bgs_sample_rois_balanced_ex', rc)
+        return inds, is_pos, valid, gt_ind, is_gt
+    rc = lib.bgs_sample_rois_balanced(*args, capi.current_stream(dev))
+    capi.check('bgs_sample_rois_balanced', rc)
+    return inds, is_pos, valid
+
+
 def decode_proposals(level_outs, level_counts, num_anchors, anchors, top_idx, top_logit, img_hw,
                      means, stds, wh_ratio_clip=16 / 1000):
     """``[N,L,nmax,5]`` decoded + clamped proposals (score = sigmoid of the top logit)."""

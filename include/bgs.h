@@ -896,6 +896,35 @@ int bgs_sample_rois_ex(const int* const* host_assigned, const int* host_counts, 
                        long long* inds, uint8_t* is_pos, uint8_t* valid, int* gt_ind, uint8_t* is_gt,
                        bgs_stream_t stream);
 
+/* The balanced RoI samplers of Libra R-CNN in one launch per batch, one workgroup per image: CombinedSampler
+ * (mmdet/core/bbox/samplers/combined_sampler.py:5-16 under BaseSampler.sample, base_sampler.py:31-78) with
+ *   pos_mode 0 = RandomSampler._sample_pos (random_sampler.py:35-43),
+ *            1 = InstanceBalancedPosSampler._sample_pos (instance_balanced_pos_sampler.py:9-41),
+ *   neg_mode 0 = RandomSampler._sample_neg (random_sampler.py:45-53),
+ *            1 = IoUBalancedNegSampler._sample_neg + sample_via_interval (iou_balanced_neg_sampler.py:44-133).
+ * host_assigned / host_max_overlaps [N]: HOST arrays of device pointers to each image's assignment vector (int32)
+ * and its max_overlaps (float32; 1.0 on the host_gt_counts[n] GT rows in front, assign_result.py add_gt_), each
+ * host_counts[n] <= 4096 entries.  Outputs as bgs_sample_rois: inds [N, num] int64 (positives, negatives, padding;
+ * each part in candidate order), is_pos, valid [N, num] uint8.  Every quota is the reference's integer (the
+ * fractions are doubles because Python computes int(num * pos_fraction) and int(n * (1 - floor_fraction)) in
+ * double); floor_thr is compared and stepped in float32 as numpy does.  Where instance_balanced_pos_sampler.py:
+ * 30-38 fills from ALL positives (its set difference is over tensors, which hash by identity) the kernel fills
+ * from the remaining ones and returns exactly int(num * pos_fraction).  The draw is a counter-based one of
+ * (seed, *draw_counter, image, stage, candidate): the same arguments give the same bits.
+ * floor_thr >= 0 or == -1, 0 <= floor_fraction <= 1, 1 <= num_bins <= 1024. */
+int bgs_sample_rois_balanced(const int* const* host_assigned, const float* const* host_max_overlaps,
+                             const int* host_counts, const int* host_gt_counts, int N, int num,
+                             double pos_fraction, double neg_pos_ub, int pos_mode, int neg_mode, double floor_thr,
+                             double floor_fraction, int num_bins, uint64_t seed, const long long* draw_counter,
+                             long long* inds, uint8_t* is_pos, uint8_t* valid, bgs_stream_t stream);
+/* + gt_ind / is_gt as bgs_sample_rois_ex emits them (sampling_result.py:7-24); either may be NULL. */
+int bgs_sample_rois_balanced_ex(const int* const* host_assigned, const float* const* host_max_overlaps,
+                                const int* host_counts, const int* host_gt_counts, int N, int num,
+                                double pos_fraction, double neg_pos_ub, int pos_mode, int neg_mode,
+                                double floor_thr, double floor_fraction, int num_bins, uint64_t seed,
+                                const long long* draw_counter, long long* inds, uint8_t* is_pos, uint8_t* valid,
+                                int* gt_ind, uint8_t* is_gt, bgs_stream_t stream);
+
 /* Sampling keys for RandomSampler (mmdet/core/bbox/samplers/random_sampler.py:19-53) drawn on the
  *   device: out[i] = 62-bit splitmix64(seed, *draw_counter, i), i < n.  draw_counter: device int64
  *   [1] (or NULL = 0) that the caller advances between draws — constant kernel arguments under
