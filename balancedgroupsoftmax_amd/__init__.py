@@ -12,7 +12,9 @@ from .bbox_heads import DCMBBoxHead, ReweightBBoxHead
 from .config import Config, ConfigDict
 from .detectors import DCM
 from .functional import class_sum, ncm_score, sigmoid_focal_loss, sigmoid_focal_loss_elementwise
-from .losses import FocalLoss
+from .backbone import BFP
+from .functional import bbox_balanced_l1_loss, bfp_gather, bfp_scatter
+from .losses import BalancedL1Loss, FocalLoss
 from .ncm import ClassCenters, load_centers
 from .lvis_eval import LVISEval, LVISGroundTruth, ResultArrays, results2arrays, results2json
 from .ops import (DeformConv, DeformConvPack, ModulatedDeformConv, ModulatedDeformConvPack, deform_conv,
@@ -37,4 +39,5 @@ __all__ = ['BACKBONES', 'DETECTORS', 'HEADS', 'LOSSES', 'NECKS', 'ROI_EXTRACTORS
            'sigmoid_focal_loss_elementwise', 'tnorm', 'ProposalAccuracy', 'reweight_cls_newhead', 'tail_mask',
            'ResultArrays', 'results2arrays', 'packed2arrays', 'recall', 'eval_recalls', 'lvis_fast_eval_recall',
            'lvis_fast_eval_recall_percat', 'print_recall_summary', 'proposal2json', 'ncm', 'DCM',
-           'DCMBBoxHead', 'ClassCenters', 'load_centers', 'class_sum', 'ncm_score']
+           'DCMBBoxHead', 'ClassCenters', 'load_centers', 'class_sum', 'ncm_score', 'BFP', 'BalancedL1Loss',
+           'bfp_gather', 'bfp_scatter', 'bbox_balanced_l1_loss']

@@ -593,3 +593,55 @@ class FPN(nn.Module):
         for _ in range(self.num_outs - n):   # F.max_pool2d(x, 1, stride=2) == subsampling
             outs.append(outs[-1][:, ::2, ::2, :].contiguous())
         return tuple(outs)
+
+
+@NECKS.register_module
+class BFP(nn.Module):
+    """Balanced feature pyramid of Libra R-CNN (mmdet/models/necks/bfp.py:10-102), after ``FPN`` in a list neck:
+    gather the levels into one map at ``refine_level`` (adaptive max pool of the finer levels, nearest resize of the
+    coarser ones, their mean), refine it, scatter it back to every level as a residual.  The gather and the scatter are
+    one HIP launch each (``functional.bfp_gather`` / ``bfp_scatter``: csrc/bfp.hip), forward and backward; the
+    ``'conv'`` refine step is the reference's ``ConvModule`` (3x3 conv + ReLU, state-dict key ``refine.conv.weight``)
+    on the conv kernels, folded through a :class:`_FoldCache` like ``FPN``'s convs.
+
+    ``refine_type='non_local'`` (``NonLocal2D``: an attention over the ~4200 positions of the refine level, which wants
+    an fp32-faithful kernel of its own, forward and backward) is not built yet and is refused by name, as are
+    ``conv_cfg`` / ``norm_cfg``."""
+
+    def __init__(self, in_channels, num_levels, refine_level=2, refine_type=None, conv_cfg=None, norm_cfg=None):
+        super().__init__()
+        assert refine_type in [None, 'conv', 'non_local']
+        if refine_type == 'non_local':
+            raise NotImplementedError("BFP(refine_type='non_local'): the NonLocal2D attention has no HIP kernel yet "
+                                      "(the next change); None and 'conv' are built")
+        if conv_cfg is not None or norm_cfg is not None:
+            raise NotImplementedError('BFP: conv_cfg / norm_cfg other than None are not built (conv_cfg=%r, norm_cfg=%r)'
+                                      % (conv_cfg, norm_cfg))
+        if num_levels > BF.capi.BGS_BFP_MAX_LEVELS:
+            raise NotImplementedError('BFP: num_levels %d; the level table of the kernels holds at most %d'
+                                      % (num_levels, BF.capi.BGS_BFP_MAX_LEVELS))
+        if in_channels % 4 != 0:
+            raise NotImplementedError('BFP: in_channels %% 4 != 0 (in_channels = %d); a thread owns 4 channels'
+                                      % in_channels)
+        self.in_channels, self.num_levels = in_channels, num_levels
+        self.conv_cfg, self.norm_cfg = conv_cfg, norm_cfg
+        self.refine_level, self.refine_type = refine_level, refine_type
+        assert 0 <= self.refine_level < self.num_levels
+        if refine_type == 'conv':
+            self.refine = ConvModule(in_channels, in_channels, 3, padding=1)
+        self._cache = _FoldCache()
+
+    def init_weights(self):
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.xavier_uniform_(m.weight)
+                nn.init.constant_(m.bias, 0)
+
+    def forward(self, inputs):
+        """inputs: NHWC levels, finest first -> NHWC levels of the same sizes (bfp.py:71-102)."""
+        assert len(inputs) == self.num_levels
+        bsf, levels = BF.bfp_gather(inputs, self.refine_level)
+        if self.refine_type == 'conv':
+            w, b = self._cache.get(self.refine, lambda: _fold_conv_bn(self.refine.conv, None))
+            bsf = BF.conv2d_autograd(bsf, w, b, pad=1, relu=True)   # (ConvModule's default activation)
+        return BF.bfp_scatter(bsf, levels, self.refine_level)

@@ -107,7 +107,7 @@ class BBoxHead(nn.Module):
     def _loss_bbox(self, bbox_pred, labels, bbox_targets, bbox_weights, reduction_override,
                    label_weights=None, n_real=None):
         """Box branch shared by every head (bbox_head.py:117-129, gs_bbox_head_with0.py:173-185):
-        HIP gather + SmoothL1 + dense-gradient kernel, no boolean-mask indexing, no sync.
+        HIP gather + SmoothL1 / BalancedL1 + dense-gradient kernel, no boolean-mask indexing, no sync.
 
         The normaliser is the reference's ``bbox_targets.size(0)`` = the number of sampled RoIs.
         In a fixed-shape batch that is the number of REAL rows: padding slots (``label_weights``
@@ -120,11 +120,18 @@ class BBoxHead(nn.Module):
             raise NotImplementedError('loss_bbox: only the mean/avg_factor reduction used by the '
                                       'detectors is implemented in the HIP path')
         lb = self.loss_bbox
-        if type(lb).__name__ != 'SmoothL1Loss':
-            raise NotImplementedError('HIP box loss implements SmoothL1Loss only')
-        val = BF.bbox_smooth_l1_loss(bbox_pred, labels, bbox_targets, bbox_weights,
-                                     self._reg_slots(bbox_pred), beta=lb.beta,
-                                     avg_factor=bbox_targets.size(0), loss_weight=lb.loss_weight)
+        kind = type(lb).__name__
+        if kind == 'SmoothL1Loss':
+            val = BF.bbox_smooth_l1_loss(bbox_pred, labels, bbox_targets, bbox_weights,
+                                         self._reg_slots(bbox_pred), beta=lb.beta,
+                                         avg_factor=bbox_targets.size(0), loss_weight=lb.loss_weight)
+        elif kind == 'BalancedL1Loss':
+            val = BF.bbox_balanced_l1_loss(bbox_pred, labels, bbox_targets, bbox_weights,
+                                           self._reg_slots(bbox_pred), alpha=lb.alpha, gamma=lb.gamma,
+                                           beta=lb.beta, avg_factor=bbox_targets.size(0),
+                                           loss_weight=lb.loss_weight)
+        else:
+            raise NotImplementedError('HIP box loss implements SmoothL1Loss and BalancedL1Loss only, not %s' % kind)
         if label_weights is not None and label_weights.is_cuda:
             if n_real is None:      # (the GS heads pass bin 0's avg factor = max(#real rows, 1))
                 n_real = (label_weights > 0).sum().to(torch.float32).clamp(min=1.0)

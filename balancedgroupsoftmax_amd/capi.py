@@ -15,6 +15,7 @@ c_ptr = ctypes.c_void_p
 
 BGS_OK = 0
 BGS_MAX_BINS = 16
+BGS_BFP_MAX_LEVELS = 8
 
 
 class BgsLibraryError(RuntimeError):
@@ -69,6 +70,13 @@ SIGNATURES = {
     'bgs_bbox_smooth_l1_fwd_bwd': (ctypes.c_int, [c_f32p, c_i64p, c_f32p, c_f32p, ctypes.c_int,
                                                   ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                                   ctypes.c_float, c_f32p, c_f32p, c_ptr, c_ptr]),
+    'bgs_bbox_balanced_l1_fwd_bwd': (ctypes.c_int, [c_f32p, c_i64p, c_f32p, c_f32p, ctypes.c_int, ctypes.c_int]
+                                     + [ctypes.c_double] * 3 + [ctypes.c_float] * 2
+                                     + [c_f32p, c_f32p, c_ptr, c_ptr]),
+    'bgs_bfp_gather': (ctypes.c_int, [c_ptr, c_ptr] + [ctypes.c_int] * 4 + [c_f32p, c_ptr, c_ptr]),
+    'bgs_bfp_scatter': (ctypes.c_int, [c_f32p, c_ptr, c_ptr] + [ctypes.c_int] * 4 + [c_ptr, c_ptr, c_ptr]),
+    'bgs_bfp_scatter_bwd': (ctypes.c_int, [c_ptr, c_ptr, c_ptr] + [ctypes.c_int] * 4 + [c_f32p, c_ptr]),
+    'bgs_bfp_gather_bwd': (ctypes.c_int, [c_f32p, c_ptr, c_ptr, c_ptr] + [ctypes.c_int] * 4 + [c_ptr, c_ptr]),
     'bgs_fc_reg_gather': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i64p, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, c_f32p, c_ptr]),
     'bgs_conv2d_nhwc_f32': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p] + [ctypes.c_int] * 11

@@ -1,5 +1,5 @@
-// Box-regression loss (SmoothL1 on the class-specific deltas of positive RoIs), forward +
-// backward, for gfx950.
+// Box-regression loss (SmoothL1 or BalancedL1 on the class-specific deltas of positive RoIs),
+// forward + backward, for gfx950.  One kernel, templated on the element loss.
 //
 // Replaces the loss_bbox branch of GSBBoxHeadWith0.loss / BBoxHead.loss
 // (mmdet/models/bbox_heads/gs_bbox_head_with0.py:173-185, bbox_head.py:117-129):
@@ -24,22 +24,60 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kBlock = 256;
 constexpr int kMaxGrid = 4096;
 
-__device__ __forceinline__ float sl1(float d, float beta, float& grad) {
-  const float ad = fabsf(d);
-  if (ad < beta) {
-    grad = d / beta;
-    return 0.5f * ad * ad / beta;
+// Element losses: value of the loss at difference d, its derivative in `grad`.
+struct SmoothL1 {
+  // its loss-only launch walks the N rows (another partition of the sum than the gradient launch: last-bit differences)
+  static constexpr bool kLossOnlySweepsSlots = false;
+  float beta;
+  __device__ __forceinline__ float operator()(float d, float& grad) const {
+    const float ad = fabsf(d);
+    if (ad < beta) {
+      grad = d / beta;
+      return 0.5f * ad * ad / beta;
+    }
+    grad = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    return ad - 0.5f * beta;
   }
-  grad = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-  return ad - 0.5f * beta;
-}
+};
 
-// WRITE_GRAD: threads sweep all N*R float4 slots.  Otherwise only N threads (one per row).
-template <bool WRITE_GRAD>
-__global__ __launch_bounds__(kBlock) void bbox_sl1_kernel(
+// balanced_l1_loss (mmdet/models/losses/balanced_l1_loss.py:19-24), x = |d|, b = e^(gamma/alpha) - 1:
+//   x <  beta:  alpha/b (b x + 1) ln(b x / beta + 1) - alpha x
+//   x >= beta:  gamma x + gamma / b - alpha beta
+// and what autograd makes of it, times sign(d) (sign(0) = 0, torch.abs's backward; a NaN difference gives a NaN
+// gradient as there; at +-inf the slope is +-gamma, where the reference's autograd multiplies the unselected branch's
+// infinite derivative by 0 and returns NaN: INTEGRATION.md):
+//   x <  beta:  alpha ln(b x / beta + 1) + alpha (b x + 1) / (b x + beta) - alpha     (= alpha ln(b x + 1) at beta = 1)
+//   x >= beta:  gamma
+// The operations are float32 in the reference's order; b, alpha / b, gamma / b and alpha beta come from the host
+// (alpha, gamma and beta arrive as doubles, the python scalars of the config; b in double, as np.e ** (gamma / alpha) - 1
+// is; alpha / b, gamma / b and alpha * beta in double, then float, which is how torch multiplies a float32 tensor by a
+// python scalar).
+struct BalancedL1 {
+  // its loss-only launch walks the N * R slots like the gradient launch, without the stores: the same threads add the
+  // same terms in the same order, so both modes return the same bits
+  static constexpr bool kLossOnlySweepsSlots = true;
+  float beta, alpha, gamma, b, alpha_over_b, gamma_over_b, alpha_beta;
+  __device__ __forceinline__ float operator()(float d, float& grad) const {
+    const float x = fabsf(d);
+    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : d);   // (+-0 at 0; a NaN difference gives a NaN gradient)
+    if (x < beta) {
+      const float bx = b * x;
+      const float lg = logf(bx / beta + 1.f);
+      grad = sgn * (alpha * lg + alpha * (bx + 1.f) / (bx + beta) - alpha);
+      return alpha_over_b * (bx + 1.f) * lg - alpha * x;
+    }
+    grad = sgn * gamma;
+    return gamma * x + gamma_over_b - alpha_beta;
+  }
+};
+
+// WRITE_GRAD: threads sweep all N*R float4 slots (and store the gradient when dpred is given).  Otherwise only N
+// threads (one per row).
+template <bool WRITE_GRAD, class ElemLoss>
+__global__ __launch_bounds__(kBlock) void bbox_loss_kernel(
     const float* __restrict__ bbox_pred, const int64_t* __restrict__ labels,
     const float* __restrict__ targets, const float* __restrict__ bweights, int N, int R,
-    float beta, float scale, float* __restrict__ partial, float* __restrict__ dpred) {
+    ElemLoss sl1, float scale, float* __restrict__ partial, float* __restrict__ dpred) {
   float acc = 0.f;
   const size_t total = WRITE_GRAD ? (size_t)N * R : (size_t)N;
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < total;
@@ -57,13 +95,13 @@ __global__ __launch_bounds__(kBlock) void bbox_sl1_kernel(
       const f32x4 t = *reinterpret_cast<const f32x4*>(targets + (size_t)r * 4);
       const f32x4 w = *reinterpret_cast<const f32x4*>(bweights + (size_t)r * 4);
       float gx, gy, gz, gw;
-      acc += sl1(p.x - t.x, beta, gx) * w.x;
-      acc += sl1(p.y - t.y, beta, gy) * w.y;
-      acc += sl1(p.z - t.z, beta, gz) * w.z;
-      acc += sl1(p.w - t.w, beta, gw) * w.w;
+      acc += sl1(p.x - t.x, gx) * w.x;
+      acc += sl1(p.y - t.y, gy) * w.y;
+      acc += sl1(p.z - t.z, gz) * w.z;
+      acc += sl1(p.w - t.w, gw) * w.w;
       g = f32x4{gx * w.x * scale, gy * w.y * scale, gz * w.z * scale, gw * w.w * scale};
     }
-    if (WRITE_GRAD) *reinterpret_cast<f32x4*>(dpred + i * 4) = g;
+    if (WRITE_GRAD && dpred) *reinterpret_cast<f32x4*>(dpred + i * 4) = g;
   }
   // block reduce (fixed order) -> partial[blockIdx.x]
   __shared__ float sm[kBlock / BGS_WAVE];
@@ -100,12 +138,14 @@ extern "C" size_t bgs_bbox_loss_workspace_bytes(int N) {
   return (size_t)kMaxGrid * sizeof(float);
 }
 
-extern "C" int bgs_bbox_smooth_l1_fwd_bwd(const float* bbox_pred, const int64_t* labels,
-                                          const float* bbox_targets, const float* bbox_weights,
-                                          int N, int R, float beta, float avg_factor,
-                                          float loss_weight, float* loss_out, float* dbbox_pred,
-                                          void* workspace, bgs_stream_t stream) {
-  if (N < 0 || R <= 0 || !(beta > 0.f) || !(avg_factor > 0.f)) return BGS_ERR_INVALID_ARG;
+namespace {
+
+template <class ElemLoss>
+int bbox_loss_launch(const float* bbox_pred, const int64_t* labels, const float* bbox_targets,
+                     const float* bbox_weights, int N, int R, ElemLoss elem, float avg_factor,
+                     float loss_weight, float* loss_out, float* dbbox_pred, void* workspace,
+                     bgs_stream_t stream) {
+  if (N < 0 || R <= 0 || !(elem.beta > 0.f) || !(avg_factor > 0.f)) return BGS_ERR_INVALID_ARG;
   if (!loss_out || !workspace) return BGS_ERR_INVALID_ARG;
   if (N > 0 && (!bbox_pred || !labels || !bbox_targets || !bbox_weights))
     return BGS_ERR_INVALID_ARG;
@@ -115,19 +155,44 @@ extern "C" int bgs_bbox_smooth_l1_fwd_bwd(const float* bbox_pred, const int64_t*
   hipStream_t st = (hipStream_t)stream;
   float* partial = (float*)workspace;
   const float scale = loss_weight / avg_factor;
-  const size_t total = dbbox_pred ? (size_t)N * R : (size_t)N;
+  const bool sweep = dbbox_pred || ElemLoss::kLossOnlySweepsSlots;
+  const size_t total = sweep ? (size_t)N * R : (size_t)N;
   size_t grid = (total + kBlock - 1) / kBlock;
   if (grid < 1) grid = 1;
   if (grid > (size_t)kMaxGrid) grid = kMaxGrid;
-  if (dbbox_pred)
-    hipLaunchKernelGGL((bbox_sl1_kernel<true>), dim3((unsigned)grid), dim3(kBlock), 0, st,
-                       bbox_pred, labels, bbox_targets, bbox_weights, N, R, beta, scale, partial,
+  if (sweep)
+    hipLaunchKernelGGL((bbox_loss_kernel<true, ElemLoss>), dim3((unsigned)grid), dim3(kBlock), 0, st,
+                       bbox_pred, labels, bbox_targets, bbox_weights, N, R, elem, scale, partial,
                        dbbox_pred);
   else
-    hipLaunchKernelGGL((bbox_sl1_kernel<false>), dim3((unsigned)grid), dim3(kBlock), 0, st,
-                       bbox_pred, labels, bbox_targets, bbox_weights, N, R, beta, scale, partial,
+    hipLaunchKernelGGL((bbox_loss_kernel<false, ElemLoss>), dim3((unsigned)grid), dim3(kBlock), 0, st,
+                       bbox_pred, labels, bbox_targets, bbox_weights, N, R, elem, scale, partial,
                        dbbox_pred);
   hipLaunchKernelGGL(bbox_reduce_kernel, dim3(1), dim3(kBlock), 0, st, partial, (int)grid, scale,
                      loss_out);
   BGS_RETURN_LAUNCH_STATUS();
+}
+
+}  // namespace
+
+extern "C" int bgs_bbox_smooth_l1_fwd_bwd(const float* bbox_pred, const int64_t* labels,
+                                          const float* bbox_targets, const float* bbox_weights,
+                                          int N, int R, float beta, float avg_factor,
+                                          float loss_weight, float* loss_out, float* dbbox_pred,
+                                          void* workspace, bgs_stream_t stream) {
+  return bbox_loss_launch(bbox_pred, labels, bbox_targets, bbox_weights, N, R, SmoothL1{beta}, avg_factor,
+                          loss_weight, loss_out, dbbox_pred, workspace, stream);
+}
+
+extern "C" int bgs_bbox_balanced_l1_fwd_bwd(const float* bbox_pred, const int64_t* labels,
+                                            const float* bbox_targets, const float* bbox_weights,
+                                            int N, int R, double alpha, double gamma, double beta,
+                                            float avg_factor, float loss_weight, float* loss_out,
+                                            float* dbbox_pred, void* workspace, bgs_stream_t stream) {
+  if (!(alpha > 0.0) || !(gamma > 0.0) || !(beta > 0.0)) return BGS_ERR_INVALID_ARG;
+  const double b = exp(gamma / alpha) - 1.0;
+  const BalancedL1 elem{(float)beta, (float)alpha, (float)gamma, (float)b, (float)(alpha / b),
+                        (float)(gamma / b), (float)(alpha * beta)};
+  return bbox_loss_launch(bbox_pred, labels, bbox_targets, bbox_weights, N, R, elem, avg_factor,
+                          loss_weight, loss_out, dbbox_pred, workspace, stream);
 }

@@ -91,6 +91,15 @@ def roi_sampler_plan(sc):
                 floor_thr=floor_thr, floor_fraction=floor_fraction, num_bins=num_bins)
 
 
+def _init_neck(neck):
+    """A list neck is an ``nn.Sequential``: initialise each member (two_stage.py:75-80 of the reference)."""
+    if isinstance(neck, nn.Sequential):
+        for m in neck:
+            m.init_weights()
+    else:
+        neck.init_weights()
+
+
 @DETECTORS.register_module
 class TwoStageDetector(nn.Module):
 
@@ -164,7 +173,7 @@ class TwoStageDetector(nn.Module):
         # (backbone.ResNet.init_weights; reference: two_stage.py:66-68 -> resnet.py:496-499)
         self.backbone.init_weights(pretrained=pretrained)
         if self.with_neck:
-            self.neck.init_weights()
+            _init_neck(self.neck)
         if self.with_rpn:
             self.rpn_head.init_weights()
         if self.with_bbox:
@@ -990,7 +999,7 @@ class CascadeRCNN(TwoStageDetector):
     def init_weights(self, pretrained=None):
         self.backbone.init_weights(pretrained=pretrained)
         if self.with_neck:
-            self.neck.init_weights()
+            _init_neck(self.neck)
         if self.with_rpn:
             self.rpn_head.init_weights()
         for ext, head in zip(self.bbox_roi_extractor, self.bbox_head):

@@ -773,6 +773,186 @@ def bbox_smooth_l1_loss(bbox_pred, labels, bbox_targets, bbox_weights, num_reg_c
                                loss_weight)
 
 
+class _BBoxBalancedL1(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, bbox_pred, labels, bbox_targets, bbox_weights, num_reg_classes, alpha, gamma, beta,
+                avg_factor, loss_weight):
+        lib = capi.load()
+        p = _f32c(bbox_pred)
+        N = p.shape[0]
+        R = int(num_reg_classes)
+        assert p.shape[1] == 4 * R
+        dev = p.device
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        dpred = torch.empty_like(p) if bbox_pred.requires_grad else None
+        ws = _workspace(lib.bgs_bbox_loss_workspace_bytes(N), dev)
+        rc = lib.bgs_bbox_balanced_l1_fwd_bwd(
+            capi.ptr(p), capi.ptr(labels), capi.ptr(bbox_targets), capi.ptr(bbox_weights), N, R,
+            float(alpha), float(gamma), float(beta), float(avg_factor), float(loss_weight), capi.ptr(loss),
+            capi.ptr(dpred), capi.ptr(ws), capi.current_stream(dev))
+        capi.check('bgs_bbox_balanced_l1_fwd_bwd', rc)
+        ctx.dpred = dpred
+        return loss[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        if ctx.dpred is None:
+            return (None,) * 10
+        return (ctx.dpred * grad_loss,) + (None,) * 9
+
+
+def bbox_balanced_l1_loss(bbox_pred, labels, bbox_targets, bbox_weights, num_reg_classes,
+                          alpha=0.5, gamma=1.5, beta=1.0, avg_factor=None, loss_weight=1.0):
+    """``loss_weight * sum(balanced_l1(pred[pos, labels[pos]] - targets[pos]) * w[pos]) / avg``
+    (mmdet/models/losses/balanced_l1_loss.py:19-24): :func:`bbox_smooth_l1_loss` with the other element loss."""
+    _require_cuda(bbox_pred, labels, bbox_targets, bbox_weights)
+    _require_f32('bbox_balanced_l1_loss', bbox_pred=bbox_pred, bbox_targets=bbox_targets, bbox_weights=bbox_weights)
+    if not (alpha > 0 and gamma > 0 and beta > 0):
+        raise ValueError('bbox_balanced_l1_loss: alpha, gamma and beta must be > 0')
+    if avg_factor is None:
+        avg_factor = bbox_targets.shape[0]
+    return _BBoxBalancedL1.apply(bbox_pred, labels.contiguous(), _f32c(bbox_targets), _f32c(bbox_weights),
+                                 num_reg_classes, alpha, gamma, beta, avg_factor, loss_weight)
+
+
+# ----------------------------------------------------------------------------------------
+# balanced feature pyramid: gather and scatter  (mmdet/models/necks/bfp.py:74-100; csrc/bfp.hip)
+# ----------------------------------------------------------------------------------------
+def _bfp_levels(name, inputs, refine_level):
+    """Checked pyramid -> (list of contiguous fp32 NHWC levels, host ``[L, 2]`` int size table, B, C)."""
+    inputs = list(inputs)
+    L = len(inputs)
+    if L < 1:
+        raise ValueError('%s: no levels' % name)
+    if L > capi.BGS_BFP_MAX_LEVELS:
+        raise NotImplementedError('%s: %d levels; the level table of the kernels holds at most %d (num_levels)'
+                                  % (name, L, capi.BGS_BFP_MAX_LEVELS))
+    if not 0 <= refine_level < L:
+        raise ValueError('%s: refine_level %d outside [0, %d)' % (name, refine_level, L))
+    if inputs[0].dim() != 4:
+        raise ValueError('%s: level 0 is %s; every level is NHWC [B, H, W, C]' % (name, tuple(inputs[0].shape)))
+    B, C = inputs[0].shape[0], inputs[0].shape[3]
+    for i, t in enumerate(inputs):
+        if t.dim() != 4 or t.shape[0] != B or t.shape[3] != C:
+            raise ValueError('%s: level %d is %s; every level is NHWC [%d, H, W, %d]' % (name, i, tuple(t.shape), B, C))
+    if C % 4 != 0:
+        raise NotImplementedError('%s: C %% 4 != 0 (C = %d); a thread owns 4 channels (16-byte accesses)' % (name, C))
+    _require_cuda(*inputs)
+    _require_f32(name, **{'level_%d' % i: t for i, t in enumerate(inputs)})
+    hw = (ctypes.c_int * (2 * L))(*[int(v) for t in inputs for v in t.shape[1:3]])
+    return inputs, hw, B, C
+
+
+def _ptr_table(tensors):
+    """Host array of device pointers (``None`` -> NULL) for the ``host_*`` parameters of the BFP kernels."""
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _c16(t):
+    """Detached, contiguous, 16-byte aligned."""
+    t = t.detach().contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _BfpGather(torch.autograd.Function):
+    """``(x_0 .. x_{L-1}) -> (bsf, x_0 .. x_{L-1})``: the levels pass through the node unchanged, so that the gradients
+    the scatter's residual path sends to them arrive HERE and ``bgs_bfp_gather_bwd`` adds each level's own share of
+    ``d bsf`` to them in its one launch (no accumulation launches per level)."""
+
+    @staticmethod
+    def forward(ctx, refine_level, want, *xs):
+        xs_c, hw, B, C = _bfp_levels('bfp_gather', xs, refine_level)
+        ctx.set_materialize_grads(False)      # a level nobody sent a gradient to reaches the kernel as NULL, not as zeros
+        xs_c = [_c16(t) for t in xs_c]
+        L = len(xs_c)
+        hr, wr = xs_c[refine_level].shape[1:3]
+        dev = xs_c[0].device
+        bsf = torch.empty((B, hr, wr, C), dtype=torch.float32, device=dev)
+        idx = [torch.empty((B, hr, wr, C), dtype=torch.int32, device=dev) if want and i < refine_level else None
+               for i in range(L)]
+        rc = capi.load().bgs_bfp_gather(_ptr_table(xs_c), hw, L, refine_level, B, C, capi.ptr(bsf),
+                                        _ptr_table(idx) if want else None, capi.current_stream(dev))
+        capi.check('bgs_bfp_gather', rc)
+        ctx.geom = (hw, L, refine_level, B, C, [tuple(t.shape) for t in xs_c])
+        ctx.idx = idx
+        return (bsf,) + tuple(xs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *douts):
+        hw, L, refine_level, B, C, shapes = ctx.geom
+        if g is None:                         # bsf went nowhere: the levels' gradients pass by identity
+            return (None, None) + tuple(douts)
+        dev = g.device
+        g = _c16(g)
+        douts = [None if d is None else _c16(d) for d in douts]
+        dxs = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+        rc = capi.load().bgs_bfp_gather_bwd(capi.ptr(g), _ptr_table(douts), _ptr_table(ctx.idx), hw, L, refine_level,
+                                            B, C, _ptr_table(dxs), capi.current_stream(dev))
+        capi.check('bgs_bfp_gather_bwd', rc)
+        return (None, None) + tuple(dxs)
+
+
+class _BfpScatter(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, refine_level, want, bsf, *xs):
+        xs_c, hw, B, C = _bfp_levels('bfp_scatter', xs, refine_level)
+        _require_cuda(bsf)
+        _require_f32('bfp_scatter', bsf=bsf)
+        if tuple(bsf.shape) != tuple(xs_c[refine_level].shape):
+            raise ValueError('bfp_scatter: bsf is %s, the refine level %s' % (tuple(bsf.shape),
+                                                                               tuple(xs_c[refine_level].shape)))
+        xs_c = [_c16(t) for t in xs_c]
+        bsf_c = _c16(bsf)
+        L = len(xs_c)
+        dev = bsf_c.device
+        outs = [torch.empty_like(t) for t in xs_c]
+        idx = [torch.empty(t.shape, dtype=torch.int32, device=dev) if want and i >= refine_level else None
+               for i, t in enumerate(xs_c)]
+        rc = capi.load().bgs_bfp_scatter(capi.ptr(bsf_c), _ptr_table(xs_c), hw, L, refine_level, B, C,
+                                         _ptr_table(outs), _ptr_table(idx) if want else None,
+                                         capi.current_stream(dev))
+        capi.check('bgs_bfp_scatter', rc)
+        ctx.geom = (hw, L, refine_level, B, C, tuple(bsf_c.shape))
+        ctx.idx = idx
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *douts):
+        hw, L, refine_level, B, C, shape = ctx.geom
+        d_bsf = None
+        if ctx.needs_input_grad[2]:
+            dc = [_c16(d) for d in douts]
+            d_bsf = torch.empty(shape, dtype=torch.float32, device=dc[0].device)
+            rc = capi.load().bgs_bfp_scatter_bwd(_ptr_table(dc), _ptr_table(ctx.idx), hw, L, refine_level, B, C,
+                                                 capi.ptr(d_bsf), capi.current_stream(d_bsf.device))
+            capi.check('bgs_bfp_scatter_bwd', rc)
+        # d x_i = dout_i: the residual path is the identity
+        return (None, None, d_bsf) + tuple(d if need else None for d, need in zip(douts, ctx.needs_input_grad[3:]))
+
+
+def bfp_gather(inputs, refine_level):
+    """BFP step 1 (bfp.py:74-86) in one launch: ``bsf = (((0 + r_0) + r_1) + ...) / L`` with ``r_i`` the adaptive max
+    pool (``i < refine_level``) or nearest resize (``i >= refine_level``) of level ``i`` to the refine level's size.
+    fp32 NHWC levels -> ``(bsf, levels)``: hand THESE ``levels`` to :func:`bfp_scatter` — under autograd they are the
+    inputs routed through the gather's node (same storage), which lets one backward launch add the residual path's
+    gradient and the gather's own; without gradients they are the inputs and no index buffer is allocated."""
+    want = torch.is_grad_enabled() and any(t.requires_grad for t in inputs)   # (arg-max buffers only then)
+    res = _BfpGather.apply(int(refine_level), want, *inputs)
+    return res[0], tuple(res[1:])
+
+
+def bfp_scatter(bsf, inputs, refine_level):
+    """BFP step 3 (bfp.py:92-100) in one launch: ``out_i = resize_i(bsf) + x_i``, nearest for ``i < refine_level``,
+    adaptive max pool for ``i >= refine_level``.  -> tuple of fp32 NHWC levels."""
+    want = torch.is_grad_enabled() and bsf.requires_grad
+    return _BfpScatter.apply(int(refine_level), want, bsf, *inputs)
+
+
 # ----------------------------------------------------------------------------------------
 # sigmoid focal loss  (mmdet/ops/sigmoid_focal_loss, mmdet/models/losses/focal_loss.py)
 # ----------------------------------------------------------------------------------------

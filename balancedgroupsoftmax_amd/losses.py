@@ -2,7 +2,8 @@
 
 Registry keys / ctor kwargs / call signature follow the reference
 (``CrossEntropyLoss``: mmdet/models/losses/cross_entropy_loss.py:64-103,
-``SmoothL1Loss``: mmdet/models/losses/smooth_l1_loss.py:18-45); the reduction rule is the
+``SmoothL1Loss``: mmdet/models/losses/smooth_l1_loss.py:18-45, ``BalancedL1Loss``:
+mmdet/models/losses/balanced_l1_loss.py:29-69); the reduction rule is the
 reference's ``weight_reduce_loss`` (mmdet/models/losses/utils.py:26-52):
 
     weighted = elementwise * weight
@@ -134,6 +135,35 @@ class SmoothL1Loss(nn.Module):
         rows = torch.ones((pred.shape[0],), dtype=torch.int64, device=pred.device)
         val = BF.bbox_smooth_l1_loss(pred, rows, target, w, 1, beta=self.beta, avg_factor=avg,
                                      loss_weight=self.loss_weight)
+        return val if div is None else val / div
+
+
+@LOSSES.register_module
+class BalancedL1Loss(nn.Module):
+    """Registry key + ctor kwargs of the reference (balanced_l1_loss.py:29-47, Libra R-CNN): with ``x = |d|`` and
+    ``b = e^(gamma / alpha) - 1``, ``alpha / b (b x + 1) ln(b x / beta + 1) - alpha x`` for ``x < beta`` else
+    ``gamma x + gamma / b - alpha beta``.  The box heads read ``alpha`` / ``gamma`` / ``beta`` / ``loss_weight`` and run
+    ``bgs_bbox_balanced_l1_fwd_bwd`` on the class-indexed ``[N, 4C]`` predictions; a direct call on
+    ``pred / target / weight [P, 4]`` runs the same kernel in its class-agnostic form (as ``SmoothL1Loss``)."""
+
+    def __init__(self, alpha=0.5, gamma=1.5, beta=1.0, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        self.alpha, self.gamma, self.beta = alpha, gamma, beta
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None,
+                **kwargs):
+        from . import functional as BF
+        assert reduction_override in _REDUCTIONS
+        red = reduction_override or self.reduction
+        BF._require_cuda(pred, target, weight)
+        assert pred.dim() == 2 and pred.shape[1] == 4 and pred.size() == target.size() and \
+            target.numel() > 0, (tuple(pred.shape), tuple(target.shape))
+        avg, div = _avg_and_scale(pred.numel(), red, avg_factor)
+        w = torch.ones_like(pred, dtype=torch.float32) if weight is None else weight
+        rows = torch.ones((pred.shape[0],), dtype=torch.int64, device=pred.device)
+        val = BF.bbox_balanced_l1_loss(pred, rows, target, w, 1, alpha=self.alpha, gamma=self.gamma,
+                                       beta=self.beta, avg_factor=avg, loss_weight=self.loss_weight)
         return val if div is None else val / div
 
 

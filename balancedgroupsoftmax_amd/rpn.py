@@ -110,6 +110,11 @@ class RPNHead(nn.Module):
         self.use_sigmoid_cls = loss_cls.get('use_sigmoid', False)
         if not self.use_sigmoid_cls:
             raise NotImplementedError('RPN objectness: sigmoid mode only (all BAGS configs)')
+        if loss_bbox.get('type') != 'SmoothL1Loss':
+            # bgs_rpn_loss evaluates SmoothL1 and reads only loss_bbox.beta / loss_weight: any other registered box loss
+            # (BalancedL1Loss) would train SmoothL1 under its name
+            raise NotImplementedError('RPNHead: loss_bbox type %r; the fused RPN loss kernel implements SmoothL1Loss only'
+                                      % (loss_bbox.get('type'),))
         self.sampling = True
         self.cls_out_channels = 1
         self.loss_cls = build_loss(loss_cls)

@@ -196,6 +196,68 @@ int bgs_bbox_smooth_l1_fwd_bwd(const float* bbox_pred, const int64_t* labels,
                                bgs_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The same with balanced_l1_loss (mmdet/models/losses/balanced_l1_loss.py:19-24, Libra R-CNN) as the
+ *   element loss, x = |d|, b = e^(gamma / alpha) - 1 (computed on the host in double from the
+ *   double parameters, as the reference computes it from the config's python scalars; alpha / b,
+ *   gamma / b, alpha beta likewise, then rounded to float once):
+ *     x <  beta:  alpha / b * (b x + 1) * ln(b x / beta + 1) - alpha x
+ *     x >= beta:  gamma x + gamma / b - alpha beta
+ *   and the derivative autograd takes of it, times sign(d):
+ *     x <  beta:  alpha ln(b x / beta + 1) + alpha (b x + 1) / (b x + beta) - alpha
+ *     x >= beta:  gamma
+ *   A NaN difference gives a NaN loss and a NaN gradient; at +-inf the gradient is +-gamma.
+ *   Everything else (slots, dense zero gradient, R = 1, fixed-order partial sums, workspace) is
+ *   bgs_bbox_smooth_l1_fwd_bwd's: one kernel, templated on the element loss.
+ *   With dbbox_pred NULL the launch still walks the N * R slots (without the stores), so the loss is
+ *   the gradient mode's loss bit for bit.
+ *   BGS_ERR_INVALID_ARG: alpha, gamma, beta or avg_factor not > 0.
+ * ---------------------------------------------------------------------------------- */
+int bgs_bbox_balanced_l1_fwd_bwd(const float* bbox_pred, const int64_t* labels,
+                                 const float* bbox_targets, const float* bbox_weights,
+                                 int N, int R, double alpha, double gamma, double beta,
+                                 float avg_factor, float loss_weight, float* loss_out,
+                                 float* dbbox_pred, void* workspace, bgs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Balanced feature pyramid (Libra R-CNN), fp32 NHWC, every level [B, H_i, W_i, C] with one C.
+ *   host_hw [L, 2] int (host): (H_i, W_i), finest level first; host_x / host_out / host_idx /
+ *   host_dout / host_dx: HOST arrays of L device pointers (read during the call only; the level
+ *   table travels by value in the kernel arguments).  Every device pointer 16-byte aligned.
+ *   BGS_ERR_UNSUPPORTED: L > BGS_BFP_MAX_LEVELS, C % 4 != 0, a side above 32768, a level of
+ *   2^31 or more (pixel, 4-channel) items: the kernels index in 32 bits.
+ *
+ *   Rules: pool window of output o = [floor(o in / out), ceil((o + 1) in / out)), first maximum
+ *   in row-major order, a NaN wins; nearest src = min((int)floorf(dst * ((float)in / (float)out)),
+ *   in - 1) (torch's float rule, not dst * in / out); arg-max indices are int32 ih * W_in + iw.
+ *
+ * bgs_bfp_gather   replaces BFP.forward step 1 (mmdet/models/necks/bfp.py:74-86):
+ *     bsf = (((0 + r_0) + r_1) + ...) / L (a float division), r_i = adaptive max pool of x_i to
+ *     the refine size for i < refine_level, nearest resize for i >= refine_level.
+ *     host_idx NULL, or entries i < refine_level = [B, Hr, Wr, C] int32 arg-max buffers.
+ * bgs_bfp_scatter  replaces step 3 (bfp.py:92-100): out_i = resize_i(bsf) + x_i, nearest for
+ *     i < refine_level, adaptive max pool for i >= refine_level.
+ *     host_idx NULL, or entries i >= refine_level = [B, H_i, W_i, C] int32.
+ * bgs_bfp_scatter_bwd  the autograd backward of step 3 towards bsf: d_bsf [B, Hr, Wr, C] from
+ *     dout_i and the scatter's indices (d x_i = dout_i is the identity and needs no kernel).
+ * bgs_bfp_gather_bwd   the autograd backward of step 1: dx_i = dout_i + (terms of d_bsf / L that
+ *     x_i fed), host_dout NULL or entries NULL = no dout_i; the gather's indices for i < refine_level.
+ *   Both backward kernels collect in gather form, levels ascending and row-major inside a
+ *   level; no atomics, the same bits on every call.
+ * ---------------------------------------------------------------------------------- */
+#define BGS_BFP_MAX_LEVELS 8
+int bgs_bfp_gather(const void* const* host_x, const int* host_hw, int L, int refine_level, int B,
+                   int C, float* bsf, void* const* host_idx, bgs_stream_t stream);
+int bgs_bfp_scatter(const float* bsf, const void* const* host_x, const int* host_hw, int L,
+                    int refine_level, int B, int C, void* const* host_out, void* const* host_idx,
+                    bgs_stream_t stream);
+int bgs_bfp_scatter_bwd(const void* const* host_dout, const void* const* host_idx,
+                        const int* host_hw, int L, int refine_level, int B, int C, float* d_bsf,
+                        bgs_stream_t stream);
+int bgs_bfp_gather_bwd(const float* d_bsf, const void* const* host_dout,
+                       const void* const* host_idx, const int* host_hw, int L, int refine_level,
+                       int B, int C, void* const* host_dx, bgs_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Class-specific box regression for the one class per RoI that its consumers read (the box loss
  *   above and bgs_refine_boxes gather slot (r, labels[r]) of the dense fc_reg output,
  *   convfc_bbox_head.py:163-165 + bbox_head.py:117-129 / :210-239): the gather ahead of the product.
