@@ -4,7 +4,7 @@ Hand-written gfx950 HIP kernels behind a C ABI (``include/bgs.h`` -> ``libbgs.so
 from PyTorch-ROCm through the reference's own registry keys and config schema.
 """
 from . import (backbone, bbox_heads, checkpoint, config, detectors, gs_tables, losses, lvis_eval,  # noqa: F401
-               mask_heads, ncm, recall, roi_extractor, rpn, semantic_head, tnorm, train)  # (imports populate the registries)
+               mask_heads, ncm, plugins, recall, roi_extractor, rpn, semantic_head, tnorm, train)  # (imports populate the registries)
 from .apis import inference_detector, init_detector
 from .builder import (build_backbone, build_detector, build_head, build_loss, build_neck,
                       build_roi_extractor, build_shared_head)
@@ -13,8 +13,9 @@ from .config import Config, ConfigDict
 from .detectors import DCM
 from .functional import class_sum, ncm_score, sigmoid_focal_loss, sigmoid_focal_loss_elementwise
 from .backbone import BFP
-from .functional import bbox_balanced_l1_loss, bfp_gather, bfp_scatter
+from .functional import bbox_balanced_l1_loss, bfp_gather, bfp_scatter, non_local_attention
 from .losses import BalancedL1Loss, FocalLoss
+from .plugins import NonLocal2D
 from .ncm import ClassCenters, load_centers
 from .lvis_eval import LVISEval, LVISGroundTruth, ResultArrays, results2arrays, results2json
 from .ops import (DeformConv, DeformConvPack, ModulatedDeformConv, ModulatedDeformConvPack, deform_conv,
@@ -40,4 +41,4 @@ __all__ = ['BACKBONES', 'DETECTORS', 'HEADS', 'LOSSES', 'NECKS', 'ROI_EXTRACTORS
            'ResultArrays', 'results2arrays', 'packed2arrays', 'recall', 'eval_recalls', 'lvis_fast_eval_recall',
            'lvis_fast_eval_recall_percat', 'print_recall_summary', 'proposal2json', 'ncm', 'DCM',
            'DCMBBoxHead', 'ClassCenters', 'load_centers', 'class_sum', 'ncm_score', 'BFP', 'BalancedL1Loss',
-           'bfp_gather', 'bfp_scatter', 'bbox_balanced_l1_loss']
+           'bfp_gather', 'bfp_scatter', 'bbox_balanced_l1_loss', 'NonLocal2D', 'non_local_attention', 'plugins']

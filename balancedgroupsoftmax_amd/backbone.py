@@ -604,16 +604,24 @@ class BFP(nn.Module):
     ``'conv'`` refine step is the reference's ``ConvModule`` (3x3 conv + ReLU, state-dict key ``refine.conv.weight``)
     on the conv kernels, folded through a :class:`_FoldCache` like ``FPN``'s convs.
 
-    ``refine_type='non_local'`` (``NonLocal2D``: an attention over the ~4200 positions of the refine level, which wants
-    an fp32-faithful kernel of its own, forward and backward) is not built yet and is refused by name, as are
-    ``conv_cfg`` / ``norm_cfg``."""
+    ``refine_type='non_local'`` (``plugins.NonLocal2D``: an attention over the ~4200 positions of the refine level, on
+    an fp32 streaming kernel of its own, forward and backward) RUNS in ``forward`` but is still refused by name in the
+    constructor, as ``conv_cfg`` / ``norm_cfg`` are: the path is reached by attaching the module, with the arguments
+    of bfp.py:59-64 --
+
+        ``neck = BFP(C, L, r, None); neck.refine = NonLocal2D(C, reduction=1, use_scale=False);``
+        ``neck.refine_type = 'non_local'``
+
+    ``init_weights`` then visits the attached convs too (xavier, overriding the zero ``conv_out``), as the
+    reference's does."""
 
     def __init__(self, in_channels, num_levels, refine_level=2, refine_type=None, conv_cfg=None, norm_cfg=None):
         super().__init__()
         assert refine_type in [None, 'conv', 'non_local']
         if refine_type == 'non_local':
-            raise NotImplementedError("BFP(refine_type='non_local'): the NonLocal2D attention has no HIP kernel yet "
-                                      "(the next change); None and 'conv' are built")
+            raise NotImplementedError("BFP(refine_type='non_local'): the constructor builds None and 'conv'; for "
+                                      "non_local attach the block: neck = BFP(C, L, r, None); neck.refine = "
+                                      "NonLocal2D(C, reduction=1, use_scale=False); neck.refine_type = 'non_local'")
         if conv_cfg is not None or norm_cfg is not None:
             raise NotImplementedError('BFP: conv_cfg / norm_cfg other than None are not built (conv_cfg=%r, norm_cfg=%r)'
                                       % (conv_cfg, norm_cfg))
@@ -644,4 +652,8 @@ class BFP(nn.Module):
         if self.refine_type == 'conv':
             w, b = self._cache.get(self.refine, lambda: _fold_conv_bn(self.refine.conv, None))
             bsf = BF.conv2d_autograd(bsf, w, b, pad=1, relu=True)   # (ConvModule's default activation)
+        elif self.refine_type == 'non_local':
+            bsf = self.refine(bsf)                                  # (an attached plugins.NonLocal2D: see the docstring)
+        elif self.refine_type is not None:
+            raise NotImplementedError('BFP: refine_type %r' % (self.refine_type,))
         return BF.bfp_scatter(bsf, levels, self.refine_level)

@@ -77,6 +77,10 @@ SIGNATURES = {
     'bgs_bfp_scatter': (ctypes.c_int, [c_f32p, c_ptr, c_ptr] + [ctypes.c_int] * 4 + [c_ptr, c_ptr, c_ptr]),
     'bgs_bfp_scatter_bwd': (ctypes.c_int, [c_ptr, c_ptr, c_ptr] + [ctypes.c_int] * 4 + [c_f32p, c_ptr]),
     'bgs_bfp_gather_bwd': (ctypes.c_int, [c_f32p, c_ptr, c_ptr, c_ptr] + [ctypes.c_int] * 4 + [c_ptr, c_ptr]),
+    'bgs_non_local_fwd': (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_longlong] + [ctypes.c_int] * 3 + [ctypes.c_float]
+                          + [c_f32p, c_f32p, c_f32p, c_ptr]),
+    'bgs_non_local_bwd': (ctypes.c_int, [c_f32p] * 6 + [ctypes.c_longlong] + [ctypes.c_int] * 3 + [ctypes.c_float]
+                          + [c_f32p] * 3 + [ctypes.c_longlong, c_f32p, c_ptr]),
     'bgs_fc_reg_gather': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i64p, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, c_f32p, c_ptr]),
     'bgs_conv2d_nhwc_f32': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p] + [ctypes.c_int] * 11

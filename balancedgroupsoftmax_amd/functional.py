@@ -7,6 +7,7 @@ path in the product.
 """
 import ctypes
 import itertools
+import math
 import os
 
 import torch
@@ -951,6 +952,149 @@ def bfp_scatter(bsf, inputs, refine_level):
     adaptive max pool for ``i >= refine_level``.  -> tuple of fp32 NHWC levels."""
     want = torch.is_grad_enabled() and bsf.requires_grad
     return _BfpScatter.apply(int(refine_level), want, bsf, *inputs)
+
+
+# ----------------------------------------------------------------------------------------
+# NonLocal2D attention core  (mmdet/models/plugins/non_local.py:74-81, 103-108; csrc/non_local.hip)
+# ----------------------------------------------------------------------------------------
+NON_LOCAL_CHANNELS = (32, 64, 128, 256)
+
+
+def _nl_rows(t):
+    """``t [B, ..., Ci]`` as a ``[B, N, Ci]`` view with strides ``(N * ld, ld, 1)`` and a 16-byte aligned start, or None
+    where no such view exists (the caller copies)."""
+    v = t.detach()
+    B, ci = v.shape[0], v.shape[-1]
+    n = v.numel() // max(B * ci, 1)
+    try:
+        v = v.view(B, n, ci)
+    except RuntimeError:
+        return None
+    # (one position per image: the row stride is free, so it is taken to be the image stride)
+    ld = v.stride(1) if n > 1 else (v.stride(0) if B > 1 else ci)
+    ok = v.stride(2) == 1 and ld >= ci and ld % 4 == 0 and (B == 1 or v.stride(0) == n * ld) and \
+        v.data_ptr() % 16 == 0
+    if not ok:
+        return None
+    return v if v.stride(1) == ld else v.as_strided((B, n, ci), (n * ld, ld, 1))
+
+
+def _nl_check(name, theta, phi, g):
+    if theta.dim() < 3 or theta.shape != phi.shape or theta.shape != g.shape:
+        raise ValueError('%s: theta, phi and g must share one shape [B, N, Ci] or [B, H, W, Ci], got %s, %s, %s'
+                         % (name, tuple(theta.shape), tuple(phi.shape), tuple(g.shape)))
+    _require_f32(name, theta=theta, phi=phi, g=g)
+    ci = theta.shape[-1]
+    if ci not in NON_LOCAL_CHANNELS:
+        raise NotImplementedError('%s: Ci = %d (inter_channels); the kernels are built for Ci in %s'
+                                  % (name, ci, list(NON_LOCAL_CHANNELS)))
+    _require_cuda(theta, phi, g)
+    if theta.numel() == 0:
+        raise ValueError('%s: empty input %s' % (name, tuple(theta.shape)))
+    if theta.numel() >= 2 ** 31:
+        raise NotImplementedError('%s: B * N * Ci >= 2^31 (32-bit indexing)' % name)
+    if theta.shape[0] > 65535:
+        raise NotImplementedError('%s: B = %d > 65535' % (name, theta.shape[0]))
+
+
+def _nl_forward(theta, phi, g, scale):
+    """-> (y [B, N, Ci], ml [B, N, 2] = row maximum and sum, the three [B, N, Ci] views the kernel read, their row
+    stride)"""
+    views = [_nl_rows(t) for t in (theta, phi, g)]
+    if any(v is None for v in views) or len(set(v.stride(1) for v in views)) != 1:
+        B, ci = theta.shape[0], theta.shape[-1]
+        views = [_c16(t).view(B, -1, ci) for t in (theta, phi, g)]
+    th, ph, gg = views
+    B, N, ci = th.shape
+    ld = th.stride(1)               # (_nl_rows and the contiguous copies both leave (N * ld, ld, 1))
+    assert ld >= ci and all(v.stride() == (N * ld, ld, 1) or B == 1 and v.stride()[1:] == (ld, 1) for v in views)
+    y = torch.empty((B, N, ci), dtype=torch.float32, device=th.device)
+    ml = torch.empty((B, N, 2), dtype=torch.float32, device=th.device)
+    rc = capi.load().bgs_non_local_fwd(capi.ptr(th), capi.ptr(ph), capi.ptr(gg), ld, B, N, ci, scale, capi.ptr(y),
+                                       None, capi.ptr(ml), capi.current_stream(th.device))
+    capi.check('bgs_non_local_fwd', rc)
+    return y, ml, views, ld
+
+
+def _nl_backward(dy, y, ml, views, ld, scale, outs, ldd):
+    th, ph, gg = views
+    B, N, ci = th.shape
+    dy = _c16(dy).view(B, N, ci)
+    delta = torch.empty((B, N), dtype=torch.float32, device=dy.device)
+    rc = capi.load().bgs_non_local_bwd(capi.ptr(dy), capi.ptr(y), capi.ptr(ml), capi.ptr(th), capi.ptr(ph),
+                                       capi.ptr(gg), ld, B, N, ci, scale, capi.ptr(outs[0]), capi.ptr(outs[1]),
+                                       capi.ptr(outs[2]), ldd, capi.ptr(delta), capi.current_stream(dy.device))
+    capi.check('bgs_non_local_bwd', rc)
+
+
+class _NonLocalFn(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, theta, phi, g, scale):
+        y, ml, views, ld = _nl_forward(theta, phi, g, scale)
+        if any(ctx.needs_input_grad[:3]):
+            # (views of the inputs' storage, or the copies the kernel read: kept by reference, as _ConvFn keeps x)
+            ctx.kept = (y, ml, views, ld, scale, tuple(theta.shape))
+        return y.view(theta.shape)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        y, ml, views, ld, scale, shape = ctx.kept
+        B, N, ci = y.shape
+        outs = [torch.empty((B, N, ci), dtype=torch.float32, device=y.device) for _ in range(3)]
+        _nl_backward(dy, y, ml, views, ld, scale, outs, ci)
+        return tuple(o.view(shape) if need else None for o, need in zip(outs, ctx.needs_input_grad[:3])) + (None,)
+
+
+class _NonLocalPackedFn(torch.autograd.Function):
+    """``tpg [B, ..., 3 * Ci]`` = theta | phi | g side by side (the output of one conv on the concatenated filter):
+    the kernels read the three column slices in place and the backward writes the three gradients into the column
+    slices of ONE ``[B, ..., 3 * Ci]`` tensor, which is the gradient of ``tpg`` — no slicing nodes, no concatenation."""
+
+    @staticmethod
+    def forward(ctx, tpg, scale):
+        ci = tpg.shape[-1] // 3
+        t = _c16(tpg)
+        y, ml, views, ld = _nl_forward(t[..., :ci], t[..., ci:2 * ci], t[..., 2 * ci:], scale)
+        if ctx.needs_input_grad[0]:
+            ctx.kept = (y, ml, views, ld, scale, tuple(tpg.shape))
+        return y.view(tuple(tpg.shape[:-1]) + (ci,))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        y, ml, views, ld, scale, shape = ctx.kept
+        ci = y.shape[2]
+        d = torch.empty(shape, dtype=torch.float32, device=y.device)
+        _nl_backward(dy, y, ml, views, ld, scale, [d[..., :ci], d[..., ci:2 * ci], d[..., 2 * ci:]], 3 * ci)
+        return d, None
+
+
+def non_local_scale(inter_channels, use_scale=True):
+    """The ``scale`` of :func:`non_local_attention` for ``NonLocal2D(use_scale=...)`` (non_local.py:77-79):
+    ``1 / sqrt(Ci)`` computed in double (rounded to float once, where the launch takes it), or 1."""
+    return 1.0 / math.sqrt(inter_channels) if use_scale else 1.0
+
+
+def non_local_attention(theta, phi, g, scale):
+    """``y[b, i, :] = sum_j softmax_j(scale * <theta[b, i, :], phi[b, j, :]>) * g[b, j, :]``: the attention core of
+    ``NonLocal2D`` (non_local.py:74-81, 103-108, mode ``'embedded_gaussian'``) as ONE streaming launch, with an
+    autograd node (two launches, no atomics).  No ``[N, N]`` matrix is ever written.  fp32 ``[B, N, Ci]`` or
+    ``[B, H, W, Ci]`` (NHWC is already ``[N, Ci]`` row-major), ``Ci`` in ``NON_LOCAL_CHANNELS``; column slices of one
+    ``[B, H, W, 3 * Ci]`` tensor are read in place.  ``scale``: a Python float (:func:`non_local_scale`)."""
+    _nl_check('non_local_attention', theta, phi, g)
+    return _NonLocalFn.apply(theta, phi, g, float(scale))
+
+
+def non_local_attention_packed(tpg, scale):
+    """:func:`non_local_attention` on ``theta | phi | g`` packed along the last axis of one fp32 tensor
+    ``[B, ..., 3 * Ci]``; its gradient is one tensor of the same shape, written in place by the backward launches."""
+    if tpg.dim() < 3 or tpg.shape[-1] % 3 != 0:
+        raise ValueError('non_local_attention_packed: expected [B, ..., 3 * Ci], got %s' % (tuple(tpg.shape),))
+    ci = tpg.shape[-1] // 3
+    _nl_check('non_local_attention_packed', tpg[..., :ci], tpg[..., ci:2 * ci], tpg[..., 2 * ci:])
+    return _NonLocalPackedFn.apply(tpg, float(scale))
 
 
 # ----------------------------------------------------------------------------------------

@@ -1356,6 +1356,36 @@ int bgs_class_sum(const float* fea, const long long* labels, int G, int D, int C
 int bgs_ncm_score(const float* fea, const float* dots, const float* cls_score, const uint8_t* valid, int R, int D,
                   int C, float* out, int* pred_label, bgs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * The attention core of NonLocal2D (mmdet/models/plugins/non_local.py:74-81, 103-108, mode 'embedded_gaussian';
+ * csrc/non_local.hip), fp32 in / fp32 accumulate on the f32-input MFMA:
+ *     y[b, i, :] = sum_j softmax_j(scale * <theta[b, i, :], phi[b, j, :]>) * g[b, j, :]
+ *   theta / phi / g: [B, N, CI] views with ONE common row stride ld (floats, >= CI), image stride N * ld: column
+ *     slices of one [B, H, W, 3 * CI] NHWC conv output, or three dense tensors (ld = CI).  scale: a float from the
+ *     host (1 / sqrt(CI) for use_scale, else 1).  y [B, N, CI] dense.  Row statistics, each optional (NULL: not
+ *     written): lse [B, N], the row log-sum-exp of scale * S, for callers that want it (informational: nothing in
+ *     this library reads it back), and ml [B, N, 2] (8-byte aligned), its two parts, the row maximum m and
+ *     l = sum_j exp(scale * S - m) (lse = m + log l).  The backward takes ml, not lse: P = exp(scale * S - m) / l
+ *     keeps the rows of P summing to 1 to rounding, where one float of magnitude 32 .. 64 for lse costs every P of
+ *     the row 2e-6.
+ *   fwd: streams over key tiles with a running maximum and sum; the maximum is subtracted before every exp.  No
+ *     [N, N] buffer exists, in the arguments or in a workspace.
+ *   bwd: dy, y dense [B, N, CI]; dtheta / dphi / dg [B, N, CI] views with ONE common row stride ldd (image stride
+ *     N * ldd); ml as the forward left it; delta [B, N] floats of scratch (receives D_i = <dy_i, y_i>).  With
+ *     P = exp(scale * S - lse) and
+ *     dS = P * (dy g^T - D):  dtheta = scale * dS phi  (a pass over query tiles),  dphi = scale * dS^T theta and
+ *     dg = P^T dy  (a pass over key tiles).  Two launches, no atomics: two calls return the same bits.
+ *   Tails in both directions are masked: any B >= 1, N >= 1.
+ *   BGS_ERR_UNSUPPORTED: CI not in {32, 64, 128, 256}; ld or ldd not a multiple of 4 or a pointer not 16-byte aligned
+ *     (16-byte row accesses); B > 65535; N > 2^31 - 65 or B * N * CI >= 2^31 (32-bit indexing).
+ *   BGS_ERR_INVALID_ARG: a null pointer, B / N / CI < 1, ld or ldd < CI.
+ * ---------------------------------------------------------------------------------- */
+int bgs_non_local_fwd(const float* theta, const float* phi, const float* g, long long ld, int B, int N, int CI,
+                      float scale, float* y, float* lse, float* ml, bgs_stream_t stream);
+int bgs_non_local_bwd(const float* dy, const float* y, const float* ml, const float* theta, const float* phi,
+                      const float* g, long long ld, int B, int N, int CI, float scale, float* dtheta, float* dphi,
+                      float* dg, long long ldd, float* delta, bgs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
