@@ -14,7 +14,9 @@ from .detectors import DCM
 from .functional import class_sum, ncm_score, sigmoid_focal_loss, sigmoid_focal_loss_elementwise
 from .backbone import BFP
 from .functional import bbox_balanced_l1_loss, bfp_gather, bfp_scatter, non_local_attention
-from .losses import BalancedL1Loss, FocalLoss
+from .losses import BalancedL1Loss, FocalLoss, MSELoss
+from .mask_heads import MaskIoUHead
+from .detectors import MaskScoringRCNN
 from .plugins import NonLocal2D
 from .ncm import ClassCenters, load_centers
 from .lvis_eval import LVISEval, LVISGroundTruth, ResultArrays, results2arrays, results2json
@@ -41,4 +43,5 @@ __all__ = ['BACKBONES', 'DETECTORS', 'HEADS', 'LOSSES', 'NECKS', 'ROI_EXTRACTORS
            'ResultArrays', 'results2arrays', 'packed2arrays', 'recall', 'eval_recalls', 'lvis_fast_eval_recall',
            'lvis_fast_eval_recall_percat', 'print_recall_summary', 'proposal2json', 'ncm', 'DCM',
            'DCMBBoxHead', 'ClassCenters', 'load_centers', 'class_sum', 'ncm_score', 'BFP', 'BalancedL1Loss',
-           'bfp_gather', 'bfp_scatter', 'bbox_balanced_l1_loss', 'NonLocal2D', 'non_local_attention', 'plugins']
+           'bfp_gather', 'bfp_scatter', 'bbox_balanced_l1_loss', 'NonLocal2D', 'non_local_attention', 'plugins',
+           'MaskIoUHead', 'MaskScoringRCNN', 'MSELoss']

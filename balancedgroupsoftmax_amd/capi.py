@@ -256,6 +256,16 @@ SIGNATURES = {
     'bgs_mask_bce': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_ptr, c_f32p, c_ptr, c_f32p,
                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_f32p,
                                     c_f32p, c_f32p, c_f32p, c_ptr]),
+    'bgs_mask_iou_target': (ctypes.c_int, [c_ptr, c_ptr] + [ctypes.c_int] * 3 + [c_f32p, ctypes.c_int, c_ptr, c_ptr,
+                                                                                   c_f32p, c_f32p, ctypes.c_int,
+                                                                                   ctypes.c_int, ctypes.c_float, c_ptr,
+                                                                                   c_f32p, c_ptr]),
+    'bgs_mask_iou_input_fwd': (ctypes.c_int, [c_f32p, c_f32p] + [ctypes.c_int] * 4 + [c_f32p, c_ptr]),
+    'bgs_mask_iou_input_bwd': (ctypes.c_int, [c_f32p, c_f32p] + [ctypes.c_int] * 4 + [c_f32p, c_f32p, c_ptr]),
+    'bgs_mask_gt_logits_bwd': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_ptr] + [ctypes.c_int] * 4
+                               + [c_f32p, c_f32p, c_f32p, c_ptr]),
+    'bgs_mask_iou_mse_fwd_bwd': (ctypes.c_int, [c_f32p, c_ptr, c_f32p, c_ptr, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_float, c_f32p, c_ptr, c_f32p, c_ptr]),
     'bgs_topk_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     'bgs_topk_sorted_f32': (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_int,
                                            ctypes.c_int, c_f32p, c_ptr, c_ptr, c_ptr]),

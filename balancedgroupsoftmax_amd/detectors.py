@@ -343,7 +343,8 @@ class TwoStageDetector(nn.Module):
                 rois, targets = samples.rois, samples.targets
                 mask_fk = None
                 if self.with_mask and rois.is_cuda and BF.rpn_loss_fork_enabled() and not (
-                        torch.is_grad_enabled() and any(p.requires_grad for p in self.mask_head.parameters())):
+                        torch.is_grad_enabled() and any(p.requires_grad for m in self._mask_branch_modules()
+                                                        for p in m.parameters())):
                     # frozen mask branch (mask RoIAlign, four convs, deconv, targets, BCE): independent of the box
                     # head — beside it on its own stream when the step is launched eagerly
                     with BF.forked(rois.device, lane=2) as mask_fk:
@@ -383,6 +384,10 @@ class TwoStageDetector(nn.Module):
         gt_inds = samples.gt_inds[:, :max_pos].reshape(-1).contiguous()
         masks = [torch.as_tensor(m).to(device=rois.device, dtype=torch.uint8).contiguous() for m in gt_masks]
         return pos_rois, pos_labels, valid, gt_inds, masks
+
+    def _mask_branch_modules(self):
+        """The modules ``_mask_forward_train`` runs: the branch forks onto its own stream only while all are frozen."""
+        return (self.mask_head,)
 
     def _mask_forward_train(self, x, samples, gt_masks):
         """two_stage.py:228-263 on the fixed-shape positives (``_mask_inputs``)."""
@@ -942,6 +947,97 @@ class MaskRCNN(TwoStageDetector):
     """mmdet/models/detectors/mask_rcnn.py: the two-stage detector with the mask branch
     (configs/bags/gs_mask_rcnn_r50_fpn_1x_lvis.py = cfg 4)."""
     pass
+
+
+@DETECTORS.register_module
+class MaskScoringRCNN(TwoStageDetector):
+    """mmdet/models/detectors/mask_scoring_rcnn.py:9-200 (Mask Scoring R-CNN, https://arxiv.org/abs/1903.00241): Mask
+    R-CNN plus a ``MaskIoUHead`` (state-dict prefix ``mask_iou_head.``) that predicts each mask's IoU with its ground
+    truth; at test time ``mask_score = bbox_score * mask_iou`` ranks the masks (lvis_utils.py:161 reads ``seg[1]``).
+
+    Training extends the parent's mask branch on the same fixed-shape positives: the GT-class mask logits come out of
+    ``mask_gt_logits_autograd`` (undetached, as mask_scoring_rcnn.py:153-154), the mask loss is the unchanged
+    ``loss_from_features``, then ``bgs_mask_iou_input_fwd``, the head, ``bgs_mask_iou_target`` on the device bitmaps and
+    ``bgs_mask_iou_mse_fwd_bwd`` — no host read.  Padding slots (``valid == 0``) never count, and with no positive target
+    ``loss_mask_iou`` is a zero scalar with a zero gradient (the reference: the vector ``mask_iou_pred * 0``).
+
+    ``simple_test`` returns ``(bbox_results, (masks, mask_scores))``: with ``segm='rle'`` the reference's per-class
+    ``(segm_results, mask_scores)`` lists (what ``lvis_eval.results2json`` / ``results2arrays`` take), otherwise the
+    device tensors ``(probs [k, 28, 28], mask_scores [k])``."""
+
+    def __init__(self, backbone, rpn_head, bbox_roi_extractor, bbox_head, mask_roi_extractor, mask_head, train_cfg,
+                 test_cfg, neck=None, shared_head=None, mask_iou_head=None, pretrained=None):
+        if test_cfg is not None and test_cfg.get('test_mode', False):
+            raise NotImplementedError('test_mode: the two-head test exists for the plain two-stage detectors only, '
+                                      'not MaskScoringRCNN')
+        if mask_iou_head is None:
+            raise ValueError('MaskScoringRCNN needs mask_iou_head (a MaskIoUHead config)')
+        super().__init__(backbone=backbone, neck=neck, shared_head=shared_head, rpn_head=rpn_head,
+                         bbox_roi_extractor=bbox_roi_extractor, bbox_head=bbox_head,
+                         mask_roi_extractor=mask_roi_extractor, mask_head=mask_head, train_cfg=train_cfg,
+                         test_cfg=test_cfg, pretrained=pretrained)
+        self.mask_iou_head = builder.build_head(mask_iou_head)
+        self.mask_iou_head.init_weights()
+
+    def init_weights(self, pretrained=None):
+        super().init_weights(pretrained=pretrained)
+        if getattr(self, 'mask_iou_head', None) is not None:       # (not yet built inside the parent's constructor)
+            self.mask_iou_head.init_weights()
+
+    def _mask_branch_modules(self):
+        return (self.mask_head, self.mask_iou_head)
+
+    def _mask_forward_train(self, x, samples, gt_masks):
+        """mask_scoring_rcnn.py:116-162 on the fixed-shape positives."""
+        rc = self.train_cfg.rcnn
+        pos_rois, pos_labels, valid, gt_inds, masks = self._mask_inputs(samples, gt_masks, rc.sampler)
+        if self.share_roi_extractor:
+            raise NotImplementedError('share_roi_extractor=True (7x7 features for the mask head) '
+                                      'is not used by the BAGS configs')
+        head = self.mask_head
+        mask_feats = self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], pos_rois)
+        feats = head.features(mask_feats, nhwc=True)
+        mask_targets = head.get_target_fixed(pos_rois, gt_inds, valid, masks, rc)
+        losses = head.loss_from_features(feats, mask_targets, pos_labels, valid)
+        P, H, W, C = feats.shape
+        z = BF.mask_gt_logits_autograd(feats.reshape(P, H * W, C), head.conv_logits.weight.view(-1, C),
+                                       head.conv_logits.bias, head._channel(pos_labels)).view(P, H, W)
+        mask_iou_pred = self.mask_iou_head(mask_feats, z, nhwc=True)
+        mask_iou_targets = self.mask_iou_head.get_target_fixed(pos_rois, gt_inds, valid, masks, z.detach(),
+                                                               mask_targets, rc)
+        losses.update(self.mask_iou_head.loss(mask_iou_pred, mask_iou_targets, pos_labels, valid))
+        return losses
+
+    def simple_test_mask(self, x, img_meta, det_bboxes, det_labels, rescale=False, paste=False, encode=None,
+                         ctx=None):
+        """mask_scoring_rcnn.py:165-200 -> ``(masks, mask_scores)``.  The head reads the detection's class LOGIT
+        (``mask_pred[range, det_labels + 1]`` before any sigmoid, :195-197) and the boxes' scores."""
+        head, iou_head = self.mask_head, self.mask_iou_head
+        if det_bboxes.shape[0] == 0:
+            if paste:
+                return ([[] for _ in range(head.num_classes - 1)], [[] for _ in range(head.num_classes - 1)])
+            return det_bboxes.new_zeros((0, 28, 28)), det_bboxes.new_zeros((0,))
+        boxes = det_bboxes[:, :4] * img_meta[0]['scale_factor'] if rescale else det_bboxes[:, :4]
+        rois = torch.cat([boxes.new_zeros((boxes.size(0), 1)), boxes], dim=1)
+        mask_feats = self.mask_roi_extractor(x[:self.mask_roi_extractor.num_inputs], rois)
+        feats = head.features(mask_feats, nhwc=True)
+        P, H, W, C = feats.shape
+        z = BF.mask_gt_logits(feats.reshape(P, H * W, C), head.conv_logits.weight.view(-1, C), head.conv_logits.bias,
+                              head._channel(det_labels + (0 if head.class_agnostic else 1))).view(P, H, W)
+        probs = torch.sigmoid(z)
+        mask_iou_pred = iou_head(mask_feats, z, nhwc=True)
+        if not paste:
+            inds = torch.arange(P, device=z.device)
+            return probs, mask_iou_pred[inds, det_labels + 1] * det_bboxes[:, -1]
+        segms = head.get_seg_masks(probs, boxes, det_labels, self.test_cfg.rcnn, img_meta[0]['ori_shape'],
+                                   img_meta[0]['scale_factor'], rescale, encode=encode)
+        return segms, iou_head.get_mask_scores(mask_iou_pred, det_bboxes, det_labels)
+
+    def aug_test(self, imgs, img_metas, **kwargs):
+        raise NotImplementedError('MaskScoringRCNN: simple_test ground (the reference has no aug_test for it)')
+
+    def simple_test_batch(self, img, img_metas, **kwargs):
+        raise NotImplementedError('MaskScoringRCNN: simple_test ground (one image per pass)')
 
 
 @DETECTORS.register_module

@@ -4018,3 +4018,191 @@ def mask_bce(feat, weight, bias, labels, target, valid=None):
     _require_cuda(feat, weight, bias, labels, target, valid)
     assert feat.dim() == 3 and weight.dim() == 2 and feat.shape[2] == weight.shape[1]
     return _MaskBceFn.apply(feat, weight, bias, labels, target, valid)
+
+
+# ----------------------------------------------------------------------------------------
+# Mask Scoring R-CNN branch (csrc/mask_iou.hip): targets, the head's input, the GT-channel logits with
+# their gradient, the gathered MSE loss
+# ----------------------------------------------------------------------------------------
+def _refuse_dtype(name, t, *dtypes):
+    if t.dtype not in dtypes:
+        raise TypeError('%s: dtype %s (expected %s)' % (name, t.dtype, ' or '.join(str(d) for d in dtypes)))
+
+
+def mask_iou_target(gt_masks, rois, gt_inds, valid, z, mask_targets, mask_thr_binary):
+    """``MaskIoUHead.get_target`` (maskiou_head.py:102-175) in two launches on bitmaps resident in HBM
+    (``bgs_mask_iou_target``): ``gt_masks`` / ``rois [P, >=5]`` / ``gt_inds [P]`` / ``valid [P]`` as :func:`mask_target`,
+    ``z [P, S, S]`` each RoI's own-class mask LOGITS, ``mask_targets [P, S, S]`` -> ``[P]`` float, 0 in invalid slots.
+    No host read."""
+    import ctypes
+    _require_cuda(rois, gt_inds, valid, z, mask_targets, *gt_masks)
+    N = len(gt_masks)
+    if N == 0:
+        raise ValueError('mask_iou_target: gt_masks is empty (per image a uint8 [G, H, W] tensor)')
+    Hm, Wm = int(gt_masks[0].shape[1]), int(gt_masks[0].shape[2])
+    for m in gt_masks:
+        _refuse_dtype('mask_iou_target: gt_masks', m, torch.uint8)
+        if m.dim() != 3 or tuple(m.shape[1:]) != (Hm, Wm) or not m.is_contiguous():
+            raise ValueError('mask_iou_target: gt_masks are contiguous [G, %d, %d] bitmaps, got %s'
+                             % (Hm, Wm, tuple(m.shape)))
+    _refuse_dtype('mask_iou_target: z', z, torch.float32)
+    _refuse_dtype('mask_iou_target: mask_targets', mask_targets, torch.float32)
+    _refuse_dtype('mask_iou_target: rois', rois, torch.float32)
+    P = int(rois.shape[0])
+    if rois.dim() != 2 or rois.shape[1] < 5 or z.dim() != 3 or z.shape[1] != z.shape[2] or \
+            tuple(z.shape) != tuple(mask_targets.shape) or z.shape[0] != P or gt_inds.numel() != P or \
+            (valid is not None and valid.numel() != P):
+        raise ValueError('mask_iou_target: rois [P, >=5], gt_inds [P], valid [P], z and mask_targets [P, S, S]; got '
+                         '%s %s %s %s %s' % (tuple(rois.shape), tuple(gt_inds.shape),
+                                             None if valid is None else tuple(valid.shape), tuple(z.shape),
+                                             tuple(mask_targets.shape)))
+    lib = capi.load()
+    rois, z, mt = _f32c(rois), _f32c(z), _f32c(mask_targets)
+    gt_inds = gt_inds.to(torch.int32).contiguous()
+    v8 = None if valid is None else valid.to(torch.uint8).contiguous()
+    out = torch.empty((P,), dtype=torch.float32, device=rois.device)
+    total = sum(int(m.shape[0]) for m in gt_masks)
+    areas = torch.empty((max(total, 1),), dtype=torch.int64, device=rois.device)
+    ptrs = (ctypes.c_void_p * N)(*[m.data_ptr() if m.numel() else None for m in gt_masks])
+    ng = (ctypes.c_int * N)(*[int(m.shape[0]) for m in gt_masks])
+    rc = lib.bgs_mask_iou_target(ptrs, ng, N, Hm, Wm, capi.ptr(rois), int(rois.shape[1]), capi.ptr(gt_inds),
+                                 capi.ptr(v8), capi.ptr(z), capi.ptr(mt), P, int(z.shape[1]), float(mask_thr_binary),
+                                 capi.ptr(areas), capi.ptr(out), capi.current_stream(rois.device))
+    capi.check('bgs_mask_iou_target', rc)
+    return out
+
+
+class _MaskIouInputFn(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, feat, z):
+        lib = capi.load()
+        f, zz = _f32c(feat), _f32c(z)
+        P, h, w, C = f.shape
+        out = torch.empty((P, h, w, C + 4), dtype=torch.float32, device=f.device)
+        rc = lib.bgs_mask_iou_input_fwd(capi.ptr(f), capi.ptr(zz), P, h, w, C, capi.ptr(out),
+                                        capi.current_stream(f.device))
+        capi.check('bgs_mask_iou_input_fwd', rc)
+        ctx.save_for_backward(zz)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dx):
+        zz, = ctx.saved_tensors
+        lib = capi.load()
+        dx = _f32c(dx)
+        P, h, w, Cp = dx.shape
+        dfeat = torch.empty((P, h, w, Cp - 4), dtype=torch.float32, device=dx.device) \
+            if ctx.needs_input_grad[0] else None
+        dz = torch.empty_like(zz) if ctx.needs_input_grad[1] else None
+        rc = lib.bgs_mask_iou_input_bwd(capi.ptr(dx), capi.ptr(zz), P, h, w, Cp - 4, capi.ptr(dfeat), capi.ptr(dz),
+                                        capi.current_stream(dx.device))
+        capi.check('bgs_mask_iou_input_bwd', rc)
+        return dfeat, dz
+
+
+def mask_iou_input(feat, z):
+    """The input of ``MaskIoUHead``'s first conv (maskiou_head.py:78-81) in one launch each way: ``feat [P, h, w, C]``
+    NHWC mask RoI features, ``z [P, 2h, 2w]`` mask logits -> ``[P, h, w, C + 4]``: the features, ``max_pool2x2(sigmoid(z))``
+    in channel ``C``, zeros above (the conv kernels need ``Cin % 4 == 0``)."""
+    _require_cuda(feat, z)
+    _refuse_dtype('mask_iou_input: feat', feat, torch.float32)
+    _refuse_dtype('mask_iou_input: z', z, torch.float32)
+    if feat.dim() != 4 or z.dim() != 3 or tuple(z.shape) != (feat.shape[0], 2 * feat.shape[1], 2 * feat.shape[2]):
+        raise ValueError('mask_iou_input: feat [P, h, w, C] and z [P, 2h, 2w], got %s and %s'
+                         % (tuple(feat.shape), tuple(z.shape)))
+    if feat.shape[3] % 4 != 0:
+        raise NotImplementedError('mask_iou_input: C % 4 != 0 (C = {})'.format(feat.shape[3]))
+    return _MaskIouInputFn.apply(feat, z)
+
+
+class _MaskGtLogitsFn(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, feat, weight, bias, labels):
+        lab = labels.to(torch.int64).contiguous()
+        ctx.save_for_backward(feat, weight, lab)
+        ctx.has_bias = bias is not None
+        return mask_gt_logits(feat, weight, bias, lab)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dz):
+        feat, weight, lab = ctx.saved_tensors
+        lib = capi.load()
+        f, w, dz = _f32c(feat), _f32c(weight), _f32c(dz)
+        P, pix, C = f.shape
+        need = ctx.needs_input_grad
+        dfeat = torch.empty_like(f) if need[0] else None
+        dw = torch.zeros_like(w) if need[1] else None
+        db = torch.zeros((w.shape[0],), dtype=torch.float32, device=f.device) if ctx.has_bias and need[2] else None
+        rc = lib.bgs_mask_gt_logits_bwd(capi.ptr(dz), capi.ptr(f), capi.ptr(w), capi.ptr(lab), P, pix, C, w.shape[0],
+                                        capi.ptr(dfeat), capi.ptr(dw), capi.ptr(db), capi.current_stream(f.device))
+        capi.check('bgs_mask_gt_logits_bwd', rc)
+        return dfeat, dw, db, None
+
+
+def mask_gt_logits_autograd(feat, weight, bias, labels):
+    """:func:`mask_gt_logits` with its gradient (``bgs_mask_gt_logits_bwd``): the reference feeds
+    ``mask_pred[range, pos_labels]`` to the MaskIoU head undetached (mask_scoring_rcnn.py:153-154).  Rows of
+    ``weight.grad`` / ``bias.grad`` shared by several RoIs are accumulated with fp32 atomics (as ``mask_bce``)."""
+    _require_cuda(feat, weight, bias, labels)
+    _refuse_dtype('mask_gt_logits_autograd: feat', feat, torch.float32)
+    _refuse_dtype('mask_gt_logits_autograd: weight', weight, torch.float32)
+    if feat.dim() != 3 or weight.dim() != 2 or feat.shape[2] != weight.shape[1] or labels.numel() != feat.shape[0]:
+        raise ValueError('mask_gt_logits_autograd: feat [P, pixels, C], weight [K, C], labels [P]; got %s %s %s'
+                         % (tuple(feat.shape), tuple(weight.shape), tuple(labels.shape)))
+    if feat.shape[2] % 4 != 0 or feat.shape[2] > 1024:
+        raise NotImplementedError('mask_gt_logits_autograd: C % 4 != 0 or C > 1024 (C = {})'.format(feat.shape[2]))
+    return _MaskGtLogitsFn.apply(feat, weight, bias, labels)
+
+
+class _MaskIouMseFn(torch.autograd.Function):
+    """loss[1] = loss_weight * mean over the kept rows of (pred[p, label_p] - target_p)^2; the dense gradient comes
+    from the same launch (scaled by the upstream scalar after)."""
+
+    @staticmethod
+    def forward(ctx, pred, labels, targets, valid, loss_weight, positive_only=True):
+        lib = capi.load()
+        pr, tg = _f32c(pred), _f32c(targets)
+        P, K = pr.shape
+        lab = None if labels is None else labels.to(torch.int64).contiguous()
+        v8 = None if valid is None else valid.to(torch.uint8).contiguous()
+        out = torch.empty((1,), dtype=torch.float32, device=pr.device)
+        grad = torch.empty_like(pr) if ctx.needs_input_grad[0] else None
+        rc = lib.bgs_mask_iou_mse_fwd_bwd(capi.ptr(pr), capi.ptr(lab), capi.ptr(tg), capi.ptr(v8), P, K,
+                                          int(bool(positive_only)), float(loss_weight), capi.ptr(out), None, capi.ptr(grad),
+                                          capi.current_stream(pr.device))
+        capi.check('bgs_mask_iou_mse_fwd_bwd', rc)
+        ctx.grad = grad
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return (None if ctx.grad is None else ctx.grad * g.reshape(()), None, None, None, None, None)
+
+
+def mask_iou_mse_loss(pred, targets, labels=None, valid=None, loss_weight=1.0, positive_only=True):
+    """``MaskIoUHead.loss`` + ``MSELoss`` (maskiou_head.py:92-99, mse_loss.py) in one launch: ``pred [P, K]`` with
+    ``labels [P]`` (the column of each row) or the already gathered ``pred [P]`` without; rows with ``valid`` and
+    ``target > 0`` are kept (NaN is not ``> 0``; ``positive_only=False``, the plain ``MSELoss``, keeps every valid
+    row) -> ``loss_weight * mean (pred - target)^2`` as ``[1]``, 0 with a zero gradient when no row is kept.  Fixed
+    summation order; the count stays on the device."""
+    _require_cuda(pred, targets, labels, valid)
+    _refuse_dtype('mask_iou_mse_loss: pred', pred, torch.float32)
+    _refuse_dtype('mask_iou_mse_loss: targets', targets, torch.float32)
+    if labels is None:
+        if pred.dim() != 1:
+            raise ValueError('mask_iou_mse_loss: without labels pred is the gathered [P], got %s' % (tuple(pred.shape),))
+        pred = pred.reshape(-1, 1)
+    else:
+        _refuse_dtype('mask_iou_mse_loss: labels', labels, torch.int64, torch.int32)
+    P = pred.shape[0]
+    if pred.dim() != 2 or targets.dim() != 1 or targets.numel() != P or \
+            (labels is not None and labels.numel() != P) or (valid is not None and valid.numel() != P):
+        raise ValueError('mask_iou_mse_loss: pred [P, K], targets / labels / valid [P]; got %s %s %s %s'
+                         % (tuple(pred.shape), tuple(targets.shape), None if labels is None else tuple(labels.shape),
+                            None if valid is None else tuple(valid.shape)))
+    return _MaskIouMseFn.apply(pred, labels, targets, valid, float(loss_weight), bool(positive_only))

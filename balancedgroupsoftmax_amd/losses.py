@@ -168,6 +168,30 @@ class BalancedL1Loss(nn.Module):
 
 
 @LOSSES.register_module
+class MSELoss(nn.Module):
+    """Registry key + ctor kwargs of the reference (mse_loss.py:10-25).  ``MaskIoUHead.loss`` reads ``loss_weight`` and
+    runs ``bgs_mask_iou_mse_fwd_bwd`` with its gather and row selection; a direct call on ``pred / target [N]`` runs the
+    same kernel with the identity gather, every row kept (``weight`` / ``avg_factor`` have no fused form)."""
+
+    def __init__(self, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        if reduction != 'mean':
+            raise NotImplementedError("MSELoss: reduction=%r (the fused kernel returns the 'mean' scalar)"
+                                      % (reduction,))
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None):
+        from . import functional as BF
+        if weight is not None or avg_factor is not None:
+            raise NotImplementedError('MSELoss: weight / avg_factor (MaskIoUHead passes neither)')
+        BF._require_cuda(pred, target)
+        if pred.dim() != 1 or pred.size() != target.size():
+            raise ValueError('MSELoss: pred and target [N], got %s and %s' % (tuple(pred.shape), tuple(target.shape)))
+        # every row kept: the "target > 0" selection is MaskIoUHead.loss's, not this module's
+        return BF.mask_iou_mse_loss(pred, target, loss_weight=self.loss_weight, positive_only=False).reshape(())
+
+
+@LOSSES.register_module
 class FocalLoss(nn.Module):
     """Registry key, ctor kwargs and call signature of the reference (focal_loss.py:46-90), on the fused HIP kernel
     ``bgs_sigmoid_focal_fwd_bwd`` (``reduction='none'``: the elementwise kernels).

@@ -234,6 +234,120 @@ class FCNMaskHead(nn.Module):
 
 
 @HEADS.register_module
+class MaskIoUHead(nn.Module):
+    """Mask Scoring R-CNN's MaskIoU head behind the reference's ``HEADS`` key, constructor, attributes and state-dict
+    names (mmdet/models/mask_heads/maskiou_head.py:12-190): ``convs.{i}`` are plain ``Conv2d`` (the first one
+    ``[conv_out, in_channels + 1, 3, 3]``, the last one stride 2), ``fcs.{i}``, ``fc_mask_iou``.
+
+    On the device the head takes NHWC mask RoI features.  Its input — ``cat(mask_feat, max_pool2x2(sigmoid(mask_pred)))``
+    — is one launch (``bgs_mask_iou_input_fwd``) that pads the ``in_channels + 1`` channels with zeros to a multiple of 4;
+    the first filter is re-laid-out to KRSC with the same zero padding and ``fcs.0.weight``'s columns are permuted from the
+    reference's ``(c, h, w)`` flattening to NHWC's, both once per parameter version.  The convs and FCs run in the conv /
+    GEMM kernels (bias + ReLU fused), the targets in ``bgs_mask_iou_target`` on bitmaps resident in HBM, the loss in
+    ``bgs_mask_iou_mse_fwd_bwd``: no host read anywhere in training.
+
+    ``get_target`` thresholds the mask LOGIT against ``mask_thr_binary`` (maskiou_head.py:138), not a probability: the
+    executed behaviour is the contract.  Two deviations: with no positive target the reference returns the VECTOR
+    ``mask_iou_pred * 0``, here a zero scalar ``[1]`` with a zero gradient; fixed-shape padding slots
+    (``valid == 0``) never count."""
+
+    def __init__(self, num_convs=4, num_fcs=2, roi_feat_size=14, in_channels=256, conv_out_channels=256,
+                 fc_out_channels=1024, num_classes=81, loss_iou=dict(type='MSELoss', loss_weight=0.5)):
+        super().__init__()
+        if num_convs < 1 or num_fcs < 1:
+            raise NotImplementedError('MaskIoUHead: num_convs = %d, num_fcs = %d (at least one of each: the first conv '
+                                      'takes the padded input, the first FC the NHWC flattening)' % (num_convs, num_fcs))
+        size = (roi_feat_size, roi_feat_size) if isinstance(roi_feat_size, int) else tuple(roi_feat_size)
+        if size[0] % 2 or size[1] % 2:
+            raise NotImplementedError('MaskIoUHead: roi_feat_size %r is not even (the 2x2 pool of the mask prediction '
+                                      'and the stride-2 conv assume it)' % (roi_feat_size,))
+        if in_channels % 4 or conv_out_channels % 4:
+            raise NotImplementedError('MaskIoUHead: in_channels % 4 != 0 or conv_out_channels % 4 != 0 '
+                                      '({}, {})'.format(in_channels, conv_out_channels))
+        self.in_channels, self.conv_out_channels = in_channels, conv_out_channels
+        self.fc_out_channels, self.num_classes = fc_out_channels, num_classes
+        self.fp16_enabled = False
+        self.convs = nn.ModuleList(
+            nn.Conv2d(in_channels + 1 if i == 0 else conv_out_channels, conv_out_channels, 3,
+                      stride=2 if i == num_convs - 1 else 1, padding=1) for i in range(num_convs))
+        self.pooled_size = (size[0] // 2, size[1] // 2)
+        pooled_area = self.pooled_size[0] * self.pooled_size[1]
+        self.fcs = nn.ModuleList(
+            nn.Linear(conv_out_channels * pooled_area if i == 0 else fc_out_channels, fc_out_channels)
+            for i in range(num_fcs))
+        self.fc_mask_iou = nn.Linear(fc_out_channels, num_classes)
+        self.relu = nn.ReLU()
+        self.max_pool = nn.MaxPool2d(2, 2)
+        self.loss_iou = build_loss(loss_iou)
+        self._fc0_cache = _FoldCache()
+
+    def init_weights(self):
+        """maskiou_head.py:65-75 (mmcv's kaiming_init defaults: fan_out, relu, normal; biases 0)."""
+        for conv in self.convs:
+            nn.init.kaiming_normal_(conv.weight, a=0, mode='fan_out', nonlinearity='relu')
+            nn.init.constant_(conv.bias, 0)
+        for fc in self.fcs:
+            nn.init.kaiming_uniform_(fc.weight, a=1, mode='fan_in', nonlinearity='leaky_relu')
+            nn.init.constant_(fc.bias, 0)
+        nn.init.normal_(self.fc_mask_iou.weight, 0, 0.01)
+        nn.init.constant_(self.fc_mask_iou.bias, 0)
+
+    def _fc0_weight(self):
+        """``fcs.0.weight`` as seen by the NHWC flattening: column ``(y * w + x) * C + c`` <- reference column
+        ``c * h * w + y * w + x`` (the box heads' rule for their first FC)."""
+        fc = self.fcs[0]
+
+        def build():
+            O = fc.weight.shape[0]
+            return fc.weight.float().view(O, self.conv_out_channels, -1).permute(0, 2, 1).reshape(O, -1).contiguous()
+        return self._fc0_cache.get(fc, build)
+
+    def forward(self, mask_feat, mask_pred, nhwc=False):
+        """Reference signature: ``mask_feat [P, C, h, w]`` (``nhwc=True``, the internal form: ``[P, h, w, C]``),
+        ``mask_pred [P, 2h, 2w]`` mask LOGITS of each RoI's class -> ``[P, num_classes]``."""
+        BF._require_cuda(mask_feat, mask_pred)
+        if not nhwc:
+            mask_feat = mask_feat.permute(0, 2, 3, 1).contiguous()
+        x = BF.mask_iou_input(mask_feat, mask_pred)
+        for i, conv in enumerate(self.convs):
+            w, b = cached_fold(conv, pad_cin_to=x.shape[3] if i == 0 else None)
+            x = BF.conv2d_autograd(x, w, b, stride=conv.stride[0], pad=1, relu=True)
+        x = x.reshape(x.size(0), -1)
+        for i, fc in enumerate(self.fcs):
+            x = BF.linear_autograd(x, self._fc0_weight() if i == 0 else fc.weight, fc.bias, relu=True)
+        return BF.linear_autograd(x, self.fc_mask_iou.weight, self.fc_mask_iou.bias)
+
+    def get_target(self, sampling_results, gt_masks, mask_pred, mask_targets, rcnn_train_cfg):
+        raise NotImplementedError('MaskIoUHead.get_target on sampling results (a host loop over numpy bitmaps in the '
+                                  'reference): call get_target_fixed(rois, gt_inds, valid, gt_masks, z, mask_targets, '
+                                  'rcnn_train_cfg) — bgs_mask_iou_target on device bitmaps')
+
+    def get_target_fixed(self, rois, gt_inds, valid, gt_masks, z, mask_targets, rcnn_train_cfg):
+        """``get_target`` (maskiou_head.py:102-175) for fixed-shape positives, the arguments of
+        ``FCNMaskHead.get_target_fixed`` plus ``z [P, S, S]`` (each RoI's own-class mask logits) and its
+        ``mask_targets`` -> ``[P]`` (0 in padding slots)."""
+        return BF.mask_iou_target(gt_masks, rois, gt_inds, valid, z, mask_targets,
+                                  float(rcnn_train_cfg.mask_thr_binary))
+
+    def loss(self, mask_iou_pred, mask_iou_targets, labels=None, valid=None):
+        """maskiou_head.py:92-99.  With ``labels``: ``mask_iou_pred [P, num_classes]``, the column of each row gathered
+        in the kernel; without: the reference's already gathered ``[P]`` pair."""
+        val = BF.mask_iou_mse_loss(mask_iou_pred, mask_iou_targets, labels, valid,
+                                   loss_weight=self.loss_iou.loss_weight)
+        return dict(loss_mask_iou=val)
+
+    def get_mask_scores(self, mask_iou_pred, det_bboxes, det_labels):
+        """maskiou_head.py:177-190: ``mask_score = bbox_score * mask_iou`` per class in detection order — one device
+        gather and multiply, one copy to the host."""
+        import numpy as np
+        inds = torch.arange(det_labels.size(0), device=det_labels.device)
+        packed = torch.stack([mask_iou_pred.float()[inds, det_labels + 1] * det_bboxes[:, -1].float(),
+                              det_labels.float()], dim=1).cpu().numpy()
+        scores, labels = packed[:, 0], packed[:, 1].astype(np.int64)
+        return [scores[labels == i] for i in range(self.num_classes - 1)]
+
+
+@HEADS.register_module
 class HTCMaskHead(FCNMaskHead):
     """mmdet/models/mask_heads/htc_mask_head.py:6-38: ``FCNMaskHead`` + ``conv_res`` (1x1 conv +
     ReLU) that injects the previous stage's mask feature (HTC's mask information flow).

@@ -1123,6 +1123,57 @@ int bgs_mask_bce(const float* feat, const float* weight, const float* bias, cons
                  int C, int num_classes, float* partial_out, float* dfeat, float* dweight,
                  float* dbias, bgs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Mask Scoring R-CNN branch (csrc/mask_iou.hip; MaskIoUHead, mmdet/models/mask_heads/maskiou_head.py).  Every entry
+ * point runs on the caller's stream without a host synchronisation; NULL, misaligned or out-of-range arguments are
+ * BGS_ERR_INVALID_ARG, unsupported ones BGS_ERR_UNSUPPORTED (no launch in either case); P == 0 is BGS_OK.
+ *
+ * bgs_mask_iou_target: MaskIoUHead.get_target + _get_area_ratio (maskiou_head.py:102-175).  host_masks / host_num_gt /
+ *   rois / gt_inds / valid as bgs_mask_target; z [P, S, S] = each RoI's own-class mask LOGITS (the reference compares
+ *   them, not their sigmoid, with mask_thr_binary: :138), mask_targets [P, S, S] in {0, 1}; area_workspace
+ *   [sum host_num_gt] 64-bit integers (8-byte aligned; zeroed and filled by the call: the byte sum of every whole
+ *   bitmap); targets_out [P] float, 0 in invalid slots.  With crop = the byte sum of the bitmap over rows y1..y2 and
+ *   columns x1..x2 (box truncated toward zero, upper ends clipped to the bitmap, negative coordinates clamped to 0 —
+ *   numpy would count those from the end) and area = the byte sum of the whole bitmap:
+ *     ratio = float(double(crop) / (double(area) + 1e-7)); pa = #(z > thr); ov = #(z > thr and target != 0);
+ *     ts = sum(target); full = ts / (ratio + 1e-7f); out = ov / (pa + full - ov)
+ *   — each a single correctly rounded float32 operation, no FMA contraction.
+ *
+ * bgs_mask_iou_input_fwd / _bwd: the input of MaskIoUHead's first conv (maskiou_head.py:78-81).  feat [P, h, w, C]
+ *   NHWC (C % 4 == 0), z [P, 2h, 2w] -> out [P, h, w, C + 4]: channels 0..C-1 = feat, channel C =
+ *   max_pool2x2(sigmoid(z)), channels C+1..C+3 = 0.  Backward: dx [P, h, w, C + 4] -> dfeat [P, h, w, C] (or NULL) =
+ *   dx[..., :C] and dz [P, 2h, 2w] (or NULL) = dx[..., C] s (1 - s) at the first maximum of each window in scan order
+ *   (MaxPool2d's rule), 0 at the other three elements.  feat / out / dx / dfeat 16-byte, z / dz 8-byte aligned.
+ *
+ * bgs_mask_gt_logits_bwd: the gradient of bgs_mask_gt_logits (mask_scoring_rcnn.py:153-154 feeds
+ *   mask_pred[range, pos_labels] to the MaskIoU head undetached).  dz [P, pixels], feat [P, pixels, C] (C % 4 == 0,
+ *   C <= 1024), weight [num_classes, C], labels [P]; dfeat [P, pixels, C] = dz W[label] (written), dweight
+ *   [num_classes, C] / dbias [num_classes] ACCUMULATED INTO with fp32 atomics as bgs_mask_bce does (zero them first;
+ *   rows no RoI uses are not touched; the order of the adds is not fixed).  Any of the three may be NULL.
+ *
+ * bgs_mask_iou_mse_fwd_bwd: MaskIoUHead.loss + MSELoss (maskiou_head.py:92-99, mse_loss.py:7-25).  pred [P, K],
+ *   labels [P] int64 (NULL: K must be 1, the already gathered pair), targets [P], valid [P] uint8 or NULL.  Rows with
+ *   valid, 0 <= label < K and — with positive_only != 0, MaskIoUHead.loss's selection — target > 0 (a NaN target is
+ *   not) are kept: loss_out [1] = loss_weight * sum (pred[p,
+ *   label_p] - target_p)^2 / max(count, 1); count_out [1] int or NULL; grad [P, K] or NULL (16-byte aligned) = the dense
+ *   gradient, zero off the gathered column and on rows left out.  Sums run in a fixed order (no atomics): two calls
+ *   return the same bits.  P == 0 writes loss 0 and count 0.
+ * ---------------------------------------------------------------------------------- */
+int bgs_mask_iou_target(const uint8_t* const* host_masks, const int* host_num_gt, int num_images, int mask_h,
+                        int mask_w, const float* rois, int roi_stride, const int* gt_inds, const uint8_t* valid,
+                        const float* z, const float* mask_targets, int P, int mask_size, float mask_thr_binary,
+                        unsigned long long* area_workspace, float* targets_out, bgs_stream_t stream);
+int bgs_mask_iou_input_fwd(const float* feat, const float* z, int P, int h, int w, int C, float* out,
+                           bgs_stream_t stream);
+int bgs_mask_iou_input_bwd(const float* dx, const float* z, int P, int h, int w, int C, float* dfeat, float* dz,
+                           bgs_stream_t stream);
+int bgs_mask_gt_logits_bwd(const float* dz, const float* feat, const float* weight, const long long* labels, int P,
+                           int pixels, int C, int num_classes, float* dfeat, float* dweight, float* dbias,
+                           bgs_stream_t stream);
+int bgs_mask_iou_mse_fwd_bwd(const float* pred, const long long* labels, const float* targets, const uint8_t* valid,
+                             int P, int K, int positive_only, float loss_weight, float* loss_out, int* count_out,
+                             float* grad, bgs_stream_t stream);
+
 /* LVIS evaluation (csrc/lvis_eval.hip): what tools/test_lvis.py reaches through lvis_eval -> LVISEval.evaluate
  * (lvis-api/lvis/eval.py:116-292), for every (image, category) PROBLEM of an evaluation in one launch per kernel.
  * Problem p owns detections dt_off[p] .. dt_off[p + 1] (already in descending score order), ground truths
