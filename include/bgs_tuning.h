@@ -59,7 +59,10 @@ int bgs_launch_census(int family, int reset);
 /* ---- fused GroupSoftmax head (csrc/gs_head.hip) ---------------------------------------------------
  * bgs_gs_head_debug_timestamps: buf != NULL (device, [2048][8] uint64) makes every later launch record 8
  *   shader-clock marks per workgroup (tools/gs_phase_times.py); NULL (default) switches it off.
- * bgs_gs_head_tuning: rows per workgroup (0 = default).
+ * bgs_gs_head_tuning: rows per workgroup of the one-row kernel, taken one after the other (0 = default; env
+ *   BGS_GS_HEAD_ROWS; n > 1 also keeps the multi-row variants 2 - 5 out).  Sampling and gradients are per-row results
+ *   and keep their bits; a workgroup adds its rows' loss terms before the reduction, so the LOSS terms are the same
+ *   sums in another fp32 order.
  * bgs_gs_head_variant: 1 = one row per workgroup (ballot bit planes; also what 0, the retired flag-word form, and
  *   unknown values select) | 2 / 3 = variant 1 with 2 / 4 rows per workgroup behind one shared prologue (N <= 2048) | 4 / 5 =
  *   2 / 3 with the gradient stored by the wave that owns the bin; < 0 (default): automatic — 4 for N < 1024, 5
@@ -95,7 +98,10 @@ int bgs_gs_head_variant_used(int N);
  * bgs_conv_dgrad_parity_enable: stride-2 data gradients with the GEMM rows grouped by output-pixel parity (1,
  *   default) or in the zero-upsampled form (0).  Bit-identical.
  * bgs_conv2d_wgrad_bfx_enable(0): every weight gradient on the fp32-MFMA kernel (A/B).
- * bgs_conv_bf16s_tuning (bf16-storage kernels): 0 = operands by LDS-DMA (default), 1 = through registers. */
+ * bgs_conv_bf16s_tuning (bf16-storage kernels; env BGS_BF16S_VARIANT, read once): 0 = operands by LDS-DMA into a 3-stage
+ *   ring (default) | 1 = through registers (conv_bf16s_reg_kernel) | 2 = the LDS-DMA ring with 4 stages (48 KB in flight per
+ *   workgroup, two workgroups per CU) | 3 = 2 with the next step's fragments read ahead of the MFMAs; other values select
+ *   0.  The same tile and summation order in every variant: bit-identical. */
 void bgs_conv_tuning(int tile, int bk, int splitk, int noswizzle);
 int bgs_conv_last_launch(int* tile, int* bk, int* up, int* splits);
 void bgs_conv_bfx_tuning(int tile, int splitk);
