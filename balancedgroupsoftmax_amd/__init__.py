@@ -20,7 +20,8 @@ from .detectors import MaskScoringRCNN
 from .plugins import NonLocal2D
 from .ncm import ClassCenters, load_centers
 from .lvis_eval import LVISEval, LVISGroundTruth, ResultArrays, results2arrays, results2json
-from .ops import (DeformConv, DeformConvPack, ModulatedDeformConv, ModulatedDeformConvPack, deform_conv,
+from .functional import context_block_nhwc, gc_apply, gc_channel, gc_pool
+from .ops import (ContextBlock, DeformConv, DeformConvPack, ModulatedDeformConv, ModulatedDeformConvPack, deform_conv,
                   modulated_deform_conv)
 from .post_processing import packed2arrays
 from .recall import (eval_recalls, lvis_fast_eval_recall, lvis_fast_eval_recall_percat, print_recall_summary,
@@ -44,4 +45,5 @@ __all__ = ['BACKBONES', 'DETECTORS', 'HEADS', 'LOSSES', 'NECKS', 'ROI_EXTRACTORS
            'lvis_fast_eval_recall_percat', 'print_recall_summary', 'proposal2json', 'ncm', 'DCM',
            'DCMBBoxHead', 'ClassCenters', 'load_centers', 'class_sum', 'ncm_score', 'BFP', 'BalancedL1Loss',
            'bfp_gather', 'bfp_scatter', 'bbox_balanced_l1_loss', 'NonLocal2D', 'non_local_attention', 'plugins',
-           'MaskIoUHead', 'MaskScoringRCNN', 'MSELoss']
+           'MaskIoUHead', 'MaskScoringRCNN', 'MSELoss', 'ContextBlock', 'context_block_nhwc', 'gc_pool', 'gc_channel',
+           'gc_apply']

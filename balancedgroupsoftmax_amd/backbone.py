@@ -32,7 +32,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as BF
-from .ops import OFFSET_PITCH, DeformConv
+from .ops import OFFSET_PITCH, ContextBlock, DeformConv
 from .registry import BACKBONES, NECKS
 
 
@@ -166,8 +166,9 @@ def cached_fold(conv, bn=None, pad_cin_to=None):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride=1, downsample=False, groups=1, base_width=4, dcn=None):
+    def __init__(self, inplanes, planes, stride=1, downsample=False, groups=1, base_width=4, dcn=None, gcb=None):
         super().__init__()
+        assert gcb is None or isinstance(gcb, dict)
         # ResNeXt (resnext.py:19-22): width = floor(planes * base_width / 64) * groups
         width = planes if groups == 1 else (planes * base_width // 64) * groups
         self.groups, self.width = groups, width
@@ -195,6 +196,11 @@ class Bottleneck(nn.Module):
             self.downsample = nn.Sequential(
                 nn.Conv2d(inplanes, planes * 4, 1, stride=stride, bias=False),
                 nn.BatchNorm2d(planes * 4))
+        # resnet.py:199-201: the global-context block on conv3's output, in front of the residual add
+        self.gcb = gcb
+        self.with_gcb = gcb is not None
+        if self.with_gcb:
+            self.context_block = ContextBlock(inplanes=planes * self.expansion, **gcb)
         self._cache = _FoldCache()
 
     def folded(self):
@@ -220,6 +226,9 @@ class Bottleneck(nn.Module):
         if self.with_dcn:
             raise NotImplementedError('Bottleneck.run_bf16_storage: a dcn block has no bf16-storage kernel '
                                       '(the deformable conv is fp32 only)')
+        if self.with_gcb:
+            raise NotImplementedError('Bottleneck.run_bf16_storage: a gcb block has no bf16-storage kernel '
+                                      '(the context block is fp32 only)')
         identity, fk = x, None
         if 'ds' in f:
             if x.is_cuda and BF.shortcut_fork_enabled():      # projection shortcut beside conv1 / conv2 (see run)
@@ -242,11 +251,13 @@ class Bottleneck(nn.Module):
         tail launch can emit it too (``BF.fused_c3_next_eligible``: a frozen layer1 block in front of a frozen 1x1 /
         stride-1 conv1) the result is ``(y, h)`` with ``h`` = that conv1's output; everywhere else ``y`` alone, as
         without it.  ``h``: THIS block's conv1 output, computed by the previous block's launch — conv1 is skipped."""
-        if h is not None and (x.dtype == torch.bfloat16 or self.groups > 1 or self.with_dcn or
+        if h is not None and (x.dtype == torch.bfloat16 or self.groups > 1 or self.with_dcn or self.with_gcb or
                               (torch.is_grad_enabled() and x.requires_grad)):
             raise RuntimeError('Bottleneck.run: a precomputed conv1 output is for the frozen fp32 block only')
         if x.dtype == torch.bfloat16:
             return self.run_bf16_storage(x, f)
+        if self.with_gcb:
+            return self._run_gcb(x, f)
         # Residual fork (x feeds conv1 / the projection shortcut AND the identity path): with a trainable
         # predecessor the first conv hands an alias of x to the other consumer (`passthrough`), so both
         # gradients meet in ITS backward and their sum — and the ReLU gate of x, when x is the
@@ -338,6 +349,38 @@ class Bottleneck(nn.Module):
                                   mask_input=True)
 
 
+    def _run_gcb(self, x, f):
+        """The block with a context block (resnet.py:249-264): conv3 WITHOUT residual and ReLU, then the block's three
+        launches; the residual add and the ReLU ride in the last of them (``functional.gc_apply``).  None of the fused
+        tails and none of the fork-fusion hand-overs apply: a tagged ``relu='consumers'`` input is turned into an
+        ordinary tensor first (``relu_gate``: autograd then sums the gradients of its two consumers), every ReLU inside
+        is gated by its own node, and the output is an ordinary ReLU output that the context block's backward gates
+        -- the successor sees an untagged input, as the first block behind the stem does."""
+        x = BF.relu_gate(x)
+        identity, fk = x, None
+        if 'ds' in f:
+            frozen = not (torch.is_grad_enabled() and (x.requires_grad or
+                                                       any(t.requires_grad for t in f['ds'] if t is not None)))
+            if frozen and x.is_cuda and BF.shortcut_fork_enabled():      # beside conv1 .. conv3, as in run
+                with BF.forked(x.device) as fk:
+                    identity = BF.conv2d_nhwc(x, f['ds'][0], f['ds'][1], stride=self.stride)
+            else:
+                identity = BF.conv2d_autograd(x, f['ds'][0], f['ds'][1], stride=self.stride)
+        out = BF.conv2d_autograd(x, f['c1'][0], f['c1'][1], relu=True)
+        if self.with_dcn:
+            off = BF.conv2d_autograd(out, f['off'][0], f['off'][1], stride=self.stride, pad=1)
+            out = BF.deform_conv3x3_nhwc(out, off, f['c2'][0], f['c2'][1], self.dcn_groups, stride=self.stride,
+                                         relu=True)
+        elif self.groups > 1:
+            out = BF.grouped_conv3x3_nhwc(out, f['c2'][0], f['c2'][1], self.groups, stride=self.stride, relu=True)
+        else:
+            out = BF.conv2d_autograd(out, f['c2'][0], f['c2'][1], stride=self.stride, pad=1, relu=True)
+        out = BF.conv2d_autograd(out, f['c3'][0], f['c3'][1])
+        if fk is not None:
+            fk.join()
+        return self.context_block(out, identity=identity, relu=True)
+
+
 @BACKBONES.register_module
 class ResNet(nn.Module):
     arch_settings = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
@@ -355,11 +398,14 @@ class ResNet(nn.Module):
         if dcn:
             raise NotImplementedError('dcn (deformable convolution, gs_htc_dconv_* config) has no '
                                       'kernel in this build')
-        if style != 'pytorch' or tuple(dilations) != (1, 1, 1, 1) or gcb or gen_attention:
+        if style != 'pytorch' or tuple(dilations) != (1, 1, 1, 1) or gen_attention:
             raise NotImplementedError('only the plain pytorch-style trunk of the BAGS configs')
         if norm_cfg.get('type', 'BN') != 'BN' or not norm_eval:
             raise NotImplementedError('BatchNorm in eval mode only (norm_eval=True is what every '
                                       'BAGS config uses); it is folded into the convs')
+        self.gcb, self.stage_with_gcb = gcb, stage_with_gcb
+        if gcb is not None:
+            assert len(stage_with_gcb) == num_stages      # resnet.py:424-425
         self.depth, self.num_stages = depth, num_stages
         self.out_indices, self.frozen_stages, self.norm_eval = out_indices, frozen_stages, norm_eval
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
@@ -375,7 +421,8 @@ class ResNet(nn.Module):
                 layers.append(Bottleneck(inplanes, planes, stride,
                                          downsample=(j == 0 and (stride != 1 or
                                                                  inplanes != planes * 4)),
-                                         groups=groups, base_width=base_width))
+                                         groups=groups, base_width=base_width,
+                                         gcb=gcb if gcb is not None and stage_with_gcb[i] else None))
                 inplanes = planes * 4
             name = 'layer{}'.format(i + 1)
             self.add_module(name, nn.Sequential(*layers))
@@ -415,6 +462,8 @@ class ResNet(nn.Module):
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode='fan_out', nonlinearity='relu')
+                if m.bias is not None:       # (kaiming_init's bias=0; of the trunk's convs only a context block's and
+                    nn.init.constant_(m.bias, 0)      # conv2_offset have one)
             elif isinstance(m, nn.BatchNorm2d):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
@@ -459,7 +508,8 @@ class ResNet(nn.Module):
             # (only behind a 64-wide stride-1 block — layer1 — and in front of a frozen plain block: the one case
             #  BF.fused_c3_next_eligible accepts; a trained block's fold is on the tape and is built once, by its own run)
             if nxt is not None and blk.width == 64 and blk.stride == 1 and blk.groups == 1 and not blk.with_dcn \
-                    and nxt.groups == 1 and not nxt.with_dcn and not _trainable(nxt):
+                    and not blk.with_gcb and nxt.groups == 1 and not nxt.with_dcn and not nxt.with_gcb \
+                    and not _trainable(nxt):
                 fn = nxt.folded()
             r = blk.run(x, f if f is not None else blk.folded(), next_c1=None if fn is None else fn['c1'], h=h)
             x, h = r if isinstance(r, tuple) else (r, None)

@@ -81,6 +81,15 @@ SIGNATURES = {
                           + [c_f32p, c_f32p, c_f32p, c_ptr]),
     'bgs_non_local_bwd': (ctypes.c_int, [c_f32p] * 6 + [ctypes.c_longlong] + [ctypes.c_int] * 3 + [ctypes.c_float]
                           + [c_f32p] * 3 + [ctypes.c_longlong, c_f32p, c_ptr]),
+    'bgs_gc_num_splits': (ctypes.c_int, [ctypes.c_int] * 2),
+    'bgs_gc_pool_fwd': (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int] * 4 + [c_f32p] * 3 + [c_ptr]),
+    'bgs_gc_channel_fwd': (ctypes.c_int, [c_f32p] * 2 + [ctypes.c_int] * 4 + [c_ptr] * 2 + [ctypes.c_float]
+                           + [c_f32p] * 7 + [c_ptr]),
+    'bgs_gc_apply_fwd': (ctypes.c_int, [c_f32p] * 4 + [ctypes.c_int] * 4 + [c_f32p, c_ptr]),
+    'bgs_gc_colsum_bwd': (ctypes.c_int, [c_f32p] * 3 + [ctypes.c_int] * 4 + [c_f32p] * 3 + [c_ptr]),
+    'bgs_gc_channel_bwd': (ctypes.c_int, [c_f32p] * 2 + [ctypes.c_int] * 4 + [c_ptr] * 2 + [c_f32p] * 9 + [c_ptr]),
+    'bgs_gc_dx_bwd': (ctypes.c_int, [c_f32p] * 8 + [ctypes.c_int] * 4 + [c_f32p] * 3 + [c_ptr]),
+    'bgs_gc_param_bwd': (ctypes.c_int, [ctypes.c_int] * 4 + [c_f32p] * 9 + [c_ptr] * 2 + [c_f32p] * 2 + [c_ptr]),
     'bgs_fc_reg_gather': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i64p, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int, c_f32p, c_ptr]),
     'bgs_conv2d_nhwc_f32': (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p] + [ctypes.c_int] * 11

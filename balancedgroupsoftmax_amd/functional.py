@@ -1098,6 +1098,241 @@ def non_local_attention_packed(tpg, scale):
 
 
 # ----------------------------------------------------------------------------------------
+# GCNet global-context block  (mmdet/ops/context_block.py; csrc/context_block.hip)
+# ----------------------------------------------------------------------------------------
+GC_MAX_CHANNELS = 2048
+GC_EPS = 1e-5           # nn.LayerNorm's default, which the reference's block uses
+
+
+def _gc_dims(name, x):
+    """Checked fp32 ``[B, N, C]`` / ``[B, H, W, C]`` map -> ``(B, N, C)``."""
+    if x.dim() not in (3, 4):
+        raise ValueError('%s: x is %s; expected NHWC [B, H, W, C] or [B, N, C]' % (name, tuple(x.shape)))
+    _require_f32(name, x=x)
+    C = x.shape[-1]
+    if C % 4 != 0:
+        raise NotImplementedError('%s: C %% 4 != 0 (C = %d); a thread owns 4 channels (16-byte accesses)' % (name, C))
+    if C > GC_MAX_CHANNELS:
+        raise NotImplementedError('%s: C > %d (C = %d); a wave keeps one row of x in registers'
+                                  % (name, GC_MAX_CHANNELS, C))
+    _require_cuda(x)
+    if x.numel() == 0:
+        raise ValueError('%s: empty input %s' % (name, tuple(x.shape)))
+    B = x.shape[0]
+    return B, x.numel() // (B * C), C
+
+
+def _gc_vec(name, arg, t, n):
+    """A parameter or per-image vector of ``n`` floats, detached, contiguous and 16-byte aligned (or None)."""
+    if t is None:
+        return None
+    _require_f32(name, **{arg: t})
+    _require_cuda(t)
+    if t.numel() != n:
+        raise ValueError('%s: %s is %s, expected %d values' % (name, arg, tuple(t.shape), n))
+    return _c16(t)
+
+
+def _gc_branch(name, arg, br, C):
+    """The six tensors of a ``channel_*_conv`` (conv weight and bias, LayerNorm weight and bias, conv weight and bias; the
+    ``[P, C, 1, 1]`` filters are read in place as ``[P, C]``) -> (list of contiguous tensors or None, P)."""
+    if br is None:
+        return None, 0
+    br = list(br)
+    if len(br) != 6 or br[0].dim() < 2:
+        raise ValueError('%s: %s must be (W1 [P, C], b1, ln_weight, ln_bias, W2 [C, P], b2)' % (name, arg))
+    P = br[0].shape[0]
+    sizes = (P * C, P, P, P, C * P, C)
+    return [_gc_vec(name, '%s[%d]' % (arg, i), t, n) for i, (t, n) in enumerate(zip(br, sizes))], P
+
+
+def _gc_planes(name, add, mul):
+    if add[0] is not None and mul[0] is not None and add[1] != mul[1]:
+        raise ValueError('%s: the add branch has %d planes, the mul branch %d' % (name, add[1], mul[1]))
+    return (add if add[0] is not None else mul)[1]
+
+
+def _gc_pool_launch(x, B, N, C, w_mask, b_mask, splits=None):
+    """-> (part [B, S, C], part_ml [B, S, 2], s [B, N] or None, S)"""
+    lib, dev = capi.load(), x.device
+    S = int(splits) if splits is not None else lib.bgs_gc_num_splits(B, N)
+    part = torch.empty((B, S, C), dtype=torch.float32, device=dev)
+    part_ml = torch.empty((B, S, 2), dtype=torch.float32, device=dev)
+    s = torch.empty((B, N), dtype=torch.float32, device=dev) if w_mask is not None else None
+    rc = lib.bgs_gc_pool_fwd(capi.ptr(x), capi.ptr(w_mask), capi.ptr(b_mask), B, N, C, S, capi.ptr(s), capi.ptr(part),
+                             capi.ptr(part_ml), capi.current_stream(dev))
+    capi.check('bgs_gc_pool_fwd', rc)
+    return part, part_ml, s, S
+
+
+def _gc_channel_launch(part, part_ml, S, B, C, P, add, mul, eps):
+    """-> (ctx [B, C], ml [B, 2], add term, mul term, hn_add, hn_mul, rstd)"""
+    dev = part.device
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    ctx, ml = new(B, C), new(B, 2)
+    t_add, hn_add = (new(B, C), new(B, 2, P)) if add is not None else (None, None)
+    t_mul, hn_mul = (new(B, C), new(B, 2, P)) if mul is not None else (None, None)
+    rstd = new(B, 2) if (add is not None or mul is not None) else None
+    rc = capi.load().bgs_gc_channel_fwd(
+        capi.ptr(part), capi.ptr(part_ml), S, B, C, P, None if add is None else _ptr_table(add),
+        None if mul is None else _ptr_table(mul), eps, capi.ptr(ctx), capi.ptr(ml), capi.ptr(t_add), capi.ptr(t_mul),
+        capi.ptr(hn_add), capi.ptr(hn_mul), capi.ptr(rstd), capi.current_stream(dev))
+    capi.check('bgs_gc_channel_fwd', rc)
+    return ctx, ml, t_add, t_mul, hn_add, hn_mul, rstd
+
+
+def _gc_apply_launch(x, B, N, C, t_mul, t_add, identity, relu):
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    rc = capi.load().bgs_gc_apply_fwd(capi.ptr(x), capi.ptr(t_mul), capi.ptr(t_add), capi.ptr(identity), int(bool(relu)),
+                                      B, N, C, capi.ptr(y), capi.current_stream(x.device))
+    capi.check('bgs_gc_apply_fwd', rc)
+    return y
+
+
+def gc_pool(x, w_mask=None, b_mask=None, splits=None):
+    """``spatial_pool`` of the reference's ``ContextBlock`` (context_block.py:64-88) on an fp32 NHWC map:
+    ``ctx[b, c] = sum_n softmax_n(<x_n, w_mask> + b_mask) x[b, n, c]`` (``'att'``), or the mean over the positions when
+    ``w_mask`` is None (``'avg'``).  -> ``(ctx [B, C], s [B, N] logits or None, ml [B, 2] = maximum and sum of
+    exp(s - maximum))``.  One pass over ``x`` (a row is read once) leaves per-split partials, a second small launch
+    combines them in split order.  Forward only: the differentiable form is :func:`context_block_nhwc`."""
+    B, N, C = _gc_dims('gc_pool', x)
+    w_mask = _gc_vec('gc_pool', 'w_mask', w_mask, C)
+    b_mask = _gc_vec('gc_pool', 'b_mask', b_mask, 1)
+    part, part_ml, s, S = _gc_pool_launch(_c16(x), B, N, C, w_mask, b_mask, splits)
+    ctx, ml = _gc_channel_launch(part, part_ml, S, B, C, 0, None, None, GC_EPS)[:2]
+    return ctx, s, ml
+
+
+def gc_channel(ctx, add=None, mul=None, eps=GC_EPS):
+    """``channel_add_conv`` / ``channel_mul_conv`` (context_block.py:36-51, 95-102) on ``ctx [B, C]``, both branches and
+    all images in one launch: ``W2 relu(LayerNorm(W1 ctx + b1)) + b2`` (biased variance, ``eps``), a sigmoid on the
+    ``mul`` branch.  ``add`` / ``mul``: the six tensors of a branch or None.  -> ``(add term, mul term)`` ``[B, C]``."""
+    if ctx.dim() != 2:
+        raise ValueError('gc_channel: ctx is %s; expected [B, C]' % (tuple(ctx.shape),))
+    B, _, C = _gc_dims('gc_channel', ctx.unsqueeze(1))
+    if add is None and mul is None:
+        raise ValueError('gc_channel: neither an add nor a mul branch')
+    add, mul = _gc_branch('gc_channel', 'add', add, C), _gc_branch('gc_channel', 'mul', mul, C)
+    P = _gc_planes('gc_channel', add, mul)
+    return _gc_channel_launch(_c16(ctx), None, 1, B, C, P, add[0], mul[0], float(eps))[2:4]
+
+
+def gc_apply(x, mul=None, add=None, identity=None, relu=False):
+    """``y = relu?(x * mul[b, c] + add[b, c] + identity)`` in one pass: the block's fusion (context_block.py:94-102) and
+    the bottleneck's ``out += identity; relu`` (resnet.py:255, 264).  ``mul`` / ``add`` ``[B, C]`` and ``identity``
+    (shaped like ``x``) are each optional.  Forward only."""
+    B, N, C = _gc_dims('gc_apply', x)
+    mul, add = _gc_vec('gc_apply', 'mul', mul, B * C), _gc_vec('gc_apply', 'add', add, B * C)
+    identity = _gc_vec('gc_apply', 'identity', identity, x.numel())
+    return _gc_apply_launch(_c16(x), B, N, C, mul, add, identity, relu)
+
+
+def _gc_forward(x, w_mask, b_mask, add, mul, identity, relu, eps):
+    """The three forward launches on checked, contiguous tensors -> (y, what the backward reads)."""
+    B, N, C = x.shape[0], x.numel() // (x.shape[0] * x.shape[-1]), x.shape[-1]
+    P = (add if add is not None else mul)[0].shape[0]
+    part, part_ml, s, S = _gc_pool_launch(x, B, N, C, w_mask, b_mask)
+    ctx, ml, t_add, t_mul, hn_add, hn_mul, rstd = _gc_channel_launch(part, part_ml, S, B, C, P, add, mul, eps)
+    y = _gc_apply_launch(x, B, N, C, t_mul, t_add, identity, relu)
+    return y, (B, N, C, P, S, s, ml, ctx, t_mul, hn_add, hn_mul, rstd)
+
+
+class _ContextBlockFn(torch.autograd.Function):
+    """The whole block as one node: three launches forward, four backward (two passes over the map)."""
+
+    @staticmethod
+    def forward(ctx, x, identity, relu, eps, w_mask, b_mask, *branches):
+        add = None if branches[0] is None else [_c16(t) for t in branches[:6]]
+        mul = None if branches[6] is None else [_c16(t) for t in branches[6:]]
+        xc = _c16(x)
+        wm = None if w_mask is None else _c16(w_mask)
+        bm = None if b_mask is None else _c16(b_mask)
+        y, kept = _gc_forward(xc, wm, bm, add, mul, None if identity is None else _c16(identity), relu, eps)
+        ctx.kept = (xc, y if relu else None, wm, add, mul, relu, identity is not None) + kept
+        ctx.shapes = [None if t is None else tuple(t.shape) for t in (w_mask, b_mask) + tuple(branches)]
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, y, wm, add, mul, relu, has_id, B, N, C, P, S, s, ml, cx, t_mul, hn_add, hn_mul, rstd = ctx.kept
+        lib, dev = capi.load(), x.device
+        st = capi.current_stream(dev)
+
+        def new(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        dy = _c16(dy)
+        g = torch.empty_like(dy) if relu else dy
+        part_a, part_m = new(B, S, C), (new(B, S, C) if mul is not None else None)
+        rc = lib.bgs_gc_colsum_bwd(capi.ptr(dy), capi.ptr(y), capi.ptr(x) if mul is not None else None, B, N, C, S,
+                                   capi.ptr(g) if relu else None, capi.ptr(part_a), capi.ptr(part_m), st)
+        capi.check('bgs_gc_colsum_bwd', rc)
+        dpre_a, dhz_a = (new(B, C), new(B, 2, P)) if add is not None else (None, None)
+        dpre_m, dhz_m = (new(B, C), new(B, 2, P)) if mul is not None else (None, None)
+        dctx = new(B, C)
+        rc = lib.bgs_gc_channel_bwd(capi.ptr(part_a), capi.ptr(part_m), S, B, C, P,
+                                    None if add is None else _ptr_table(add), None if mul is None else _ptr_table(mul),
+                                    capi.ptr(t_mul), capi.ptr(hn_add), capi.ptr(hn_mul), capi.ptr(rstd),
+                                    capi.ptr(dpre_a), capi.ptr(dpre_m), capi.ptr(dhz_a), capi.ptr(dhz_m),
+                                    capi.ptr(dctx), st)
+        capi.check('bgs_gc_channel_bwd', rc)
+        dx = torch.empty_like(x)
+        part_dw, part_ds = (new(B, S, C), new(B, S)) if wm is not None else (None, None)
+        rc = lib.bgs_gc_dx_bwd(capi.ptr(g), capi.ptr(x), capi.ptr(s), capi.ptr(ml), capi.ptr(cx), capi.ptr(dctx),
+                               capi.ptr(t_mul), capi.ptr(wm), B, N, C, S, capi.ptr(dx), capi.ptr(part_dw),
+                               capi.ptr(part_ds), st)
+        capi.check('bgs_gc_dx_bwd', rc)
+        sizes = (P * C, P, P, P, C * P, C)
+        d_add = [new(n) for n in sizes] if add is not None else None
+        d_mul = [new(n) for n in sizes] if mul is not None else None
+        dw_mask, db_mask = (new(C), new(1)) if wm is not None else (None, None)
+        rc = lib.bgs_gc_param_bwd(B, S, C, P, capi.ptr(cx), capi.ptr(dpre_a), capi.ptr(dpre_m), capi.ptr(hn_add),
+                                  capi.ptr(hn_mul), capi.ptr(dhz_a), capi.ptr(dhz_m), capi.ptr(part_dw),
+                                  capi.ptr(part_ds), None if d_add is None else _ptr_table(d_add),
+                                  None if d_mul is None else _ptr_table(d_mul), capi.ptr(dw_mask), capi.ptr(db_mask), st)
+        capi.check('bgs_gc_param_bwd', rc)
+        grads = [dw_mask, db_mask] + (d_add or [None] * 6) + (d_mul or [None] * 6)
+        grads = [None if (t is None or not need) else t.view(shape)
+                 for t, shape, need in zip(grads, ctx.shapes, ctx.needs_input_grad[4:])]
+        return (dx if ctx.needs_input_grad[0] else None, g if has_id and ctx.needs_input_grad[1] else None,
+                None, None) + tuple(grads)
+
+
+def context_block_nhwc(x, params, identity=None, relu=False):
+    """The reference's ``ContextBlock.forward`` (context_block.py:90-104) on an fp32 NHWC map, optionally followed by the
+    bottleneck's ``out += identity`` and ReLU (resnet.py:255, 264), as ONE autograd node: three launches forward (pool,
+    channel MLPs, apply), four backward.  ``params``: dict with ``w_mask`` / ``b_mask`` (``conv_mask``'s weight and bias;
+    ``w_mask`` None selects ``pooling_type='avg'``), ``add`` / ``mul`` (the six tensors of ``channel_add_conv`` /
+    ``channel_mul_conv``: conv, LayerNorm, conv; None for an absent branch) and optionally ``eps``.  With ``relu`` the
+    result is an ordinary ReLU output whose gate this node's backward applies."""
+    name = 'context_block_nhwc'
+    if params.get('add') is None and params.get('mul') is None:
+        raise ValueError('%s: neither an add nor a mul branch' % name)
+    B, N, C = _gc_dims(name, x)
+    w_mask, b_mask = params.get('w_mask'), params.get('b_mask')
+    if w_mask is not None and b_mask is None:
+        raise ValueError('%s: w_mask without b_mask' % name)
+    if w_mask is None:
+        b_mask = None
+    _gc_vec(name, 'w_mask', w_mask, C)
+    _gc_vec(name, 'b_mask', b_mask, 1)
+    add, mul = _gc_branch(name, 'add', params.get('add'), C), _gc_branch(name, 'mul', params.get('mul'), C)
+    _gc_planes(name, add, mul)
+    if identity is not None:
+        if tuple(identity.shape) != tuple(x.shape):
+            raise ValueError('%s: identity is %s, x %s' % (name, tuple(identity.shape), tuple(x.shape)))
+        _gc_vec(name, 'identity', identity, x.numel())
+    eps = float(params.get('eps', GC_EPS))
+    flat = (w_mask, b_mask) + tuple(params.get('add') or (None,) * 6) + tuple(params.get('mul') or (None,) * 6)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, identity) + flat):
+        return _ContextBlockFn.apply(x, identity, bool(relu), eps, *flat)
+    return _gc_forward(_c16(x), None if w_mask is None else _c16(w_mask), None if b_mask is None else _c16(b_mask),
+                       add[0], mul[0], None if identity is None else _c16(identity), bool(relu), eps)[0]
+
+
+# ----------------------------------------------------------------------------------------
 # sigmoid focal loss  (mmdet/ops/sigmoid_focal_loss, mmdet/models/losses/focal_loss.py)
 # ----------------------------------------------------------------------------------------
 def _focal_inputs(name, logits, labels, gamma, pos_shift):

@@ -1,4 +1,6 @@
-"""``DeformConv`` / ``DeformConvPack`` of the reference (mmdet/ops/dcn/deform_conv.py:190-261) over
+"""``ContextBlock`` of the reference (mmdet/ops/context_block.py) over ``functional.context_block_nhwc``
+(csrc/context_block.hip), and
+``DeformConv`` / ``DeformConvPack`` of the reference (mmdet/ops/dcn/deform_conv.py:190-261) over
 ``functional.deform_conv3x3_nhwc`` (csrc/deform_conv.hip).
 
 Constructor arguments, parameter names and shapes (``weight [Cout, Cin/groups, kh, kw]``, no bias;
@@ -123,6 +125,79 @@ class DeformConvPack(DeformConv):
     def forward(self, x):
         return deform_conv(x, self.offsets(x), self.weight, self.stride, self.padding, self.dilation,
                            self.groups, self.deformable_groups)
+
+
+class ContextBlock(nn.Module):
+    """Global-context block of GCNet: the reference's ``ContextBlock`` (mmdet/ops/context_block.py:13-104) with its
+    constructor arguments, attributes, asserts, member names (``conv_mask``, ``channel_add_conv``, ``channel_mul_conv``:
+    ``nn.Conv2d`` / ``nn.LayerNorm`` / ``nn.ReLU`` parameter containers, so its checkpoints load unchanged) and
+    ``reset_parameters``.  ``forward`` takes and returns fp32 NHWC, as the trunk does, and runs
+    ``functional.context_block_nhwc`` (csrc/context_block.hip): three launches forward, four backward.  The
+    ``[P, C, 1, 1]`` filters are read in place as ``[P, C]``."""
+
+    def __init__(self, inplanes, ratio, pooling_type='att', fusion_types=('channel_add', )):
+        super().__init__()
+        assert pooling_type in ['avg', 'att']
+        assert isinstance(fusion_types, (list, tuple))
+        valid_fusion_types = ['channel_add', 'channel_mul']
+        assert all([f in valid_fusion_types for f in fusion_types])
+        assert len(fusion_types) > 0, 'at least one fusion should be used'
+        self.inplanes = inplanes
+        self.ratio = ratio
+        self.planes = int(inplanes * ratio)
+        self.pooling_type = pooling_type
+        self.fusion_types = fusion_types
+        if self.planes < 1:
+            raise ValueError('ContextBlock: int(inplanes * ratio) = %d planes (inplanes %d, ratio %r)'
+                             % (self.planes, inplanes, ratio))
+        if inplanes % 4 != 0 or inplanes > BF.GC_MAX_CHANNELS:
+            raise NotImplementedError('ContextBlock: inplanes = %d; the kernels take inplanes %% 4 == 0 and inplanes '
+                                      '<= %d' % (inplanes, BF.GC_MAX_CHANNELS))
+        if pooling_type == 'att':
+            self.conv_mask = nn.Conv2d(inplanes, 1, kernel_size=1)
+            self.softmax = nn.Softmax(dim=2)
+        else:
+            self.avg_pool = nn.AdaptiveAvgPool2d(1)
+
+        def branch():
+            return nn.Sequential(nn.Conv2d(self.inplanes, self.planes, kernel_size=1),
+                                 nn.LayerNorm([self.planes, 1, 1]), nn.ReLU(inplace=True),
+                                 nn.Conv2d(self.planes, self.inplanes, kernel_size=1))
+        self.channel_add_conv = branch() if 'channel_add' in fusion_types else None
+        self.channel_mul_conv = branch() if 'channel_mul' in fusion_types else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        """context_block.py:54-62: kaiming (fan_in) on ``conv_mask``, zeros in the last conv of each branch, so that a
+        fresh block adds 0 (or multiplies by sigmoid(0) on the mul branch, as the reference's does)."""
+        if self.pooling_type == 'att':
+            nn.init.kaiming_normal_(self.conv_mask.weight, a=0, mode='fan_in', nonlinearity='relu')
+            nn.init.constant_(self.conv_mask.bias, 0)
+            self.conv_mask.inited = True
+        for seq in (self.channel_add_conv, self.channel_mul_conv):
+            if seq is not None:
+                nn.init.constant_(seq[-1].weight, 0)
+                nn.init.constant_(seq[-1].bias, 0)
+
+    @staticmethod
+    def _branch_tensors(seq):
+        if seq is None:
+            return None
+        return (seq[0].weight, seq[0].bias, seq[1].weight, seq[1].bias, seq[3].weight, seq[3].bias)
+
+    def kernel_params(self):
+        """The ``params`` dict of ``functional.context_block_nhwc``: the module's own parameter tensors."""
+        att = self.pooling_type == 'att'
+        eps = (self.channel_add_conv or self.channel_mul_conv)[1].eps
+        return dict(w_mask=self.conv_mask.weight if att else None, b_mask=self.conv_mask.bias if att else None,
+                    add=self._branch_tensors(self.channel_add_conv), mul=self._branch_tensors(self.channel_mul_conv),
+                    eps=eps)
+
+    def forward(self, x, identity=None, relu=False):
+        """NHWC fp32 ``x`` -> NHWC; ``identity`` / ``relu``: the bottleneck's residual add and ReLU in the same pass."""
+        if x.dim() != 4 or x.shape[-1] != self.inplanes:
+            raise ValueError('ContextBlock: x is %s; expected NHWC [B, H, W, %d]' % (tuple(x.shape), self.inplanes))
+        return BF.context_block_nhwc(x, self.kernel_params(), identity=identity, relu=relu)
 
 
 class ModulatedDeformConv(nn.Module):

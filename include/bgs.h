@@ -1437,6 +1437,62 @@ int bgs_non_local_bwd(const float* dy, const float* y, const float* ml, const fl
                       const float* g, long long ld, int B, int N, int CI, float scale, float* dtheta, float* dphi,
                       float* dg, long long ldd, float* delta, bgs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Global-context block of GCNet (mmdet/ops/context_block.py; csrc/context_block.hip), fp32 NHWC, forward and
+ * backward.  x [B, N, C] dense (N = H * W), C % 4 == 0 and C <= 2048 (BGS_ERR_UNSUPPORTED otherwise, as are
+ * B * N >= 2^31 and B * N * C / 4 >= 2^31); every map-sized pointer 16-byte aligned.  N is cut into S splits of
+ * ceil(N / S) rows (1 <= S <= min(N, 1024); bgs_gc_num_splits(B, N) is the library's choice: about 512 workgroups
+ * over the batch, 263 at B = 1, N = 1050); every per-split partial is combined in split order by the next launch.
+ * No atomics: two calls return the same bits.  No launch synchronises or allocates.
+ *
+ * bgs_gc_pool_fwd     replaces spatial_pool (context_block.py:64-88).  w_mask [C] / b_mask [1] (device): 'att',
+ *     s [B, N] receives the logits <x_n, w_mask> + b_mask; w_mask NULL: 'avg' (every row has weight 1).  A row is
+ *     read ONCE and kept in registers between the dot product and the weighted sum.  part [B, S, C] receives
+ *     sum_n exp(s_n - m_k) x_n of split k, part_ml [B, S, 2] its (m_k, sum_n exp(s_n - m_k)); the maximum is
+ *     subtracted before every exp.
+ * bgs_gc_channel_fwd  replaces the softmax's normalisation and channel_add_conv / channel_mul_conv
+ *     (context_block.py:36-51, 95-102).  ctx [B, C] = sum_k part_k exp(m_k - m) / l and ml [B, 2] = (m, l) with
+ *     m = max_k m_k, l = sum_k l_k exp(m_k - m) (part_ml NULL: S == 1 and part IS ctx).  host_add / host_mul: host
+ *     arrays of the six device pointers of a branch (W1 [P, C], b1 [P], LayerNorm weight [P], bias [P], W2 [C, P],
+ *     b2 [C]) or NULL for an absent branch: term = W2 relu(LN(W1 ctx + b1)) + b2, LayerNorm over P with the biased
+ *     variance and eps, a sigmoid on the mul branch.  add / mul [B, C]; hn_* [B, 2, P] receives the normalised
+ *     value and the ReLU output, rstd [B, 2] the reciprocal deviations (by position among the present branches).
+ *     One launch for all images and both branches.  Any P >= 1.
+ * bgs_gc_apply_fwd    y = relu?(x * mul[b, c] + add[b, c] + identity): the block's fusion (context_block.py:94-102)
+ *     and the bottleneck's out += identity; relu (resnet.py:255, 264).  mul, add, identity: each may be NULL.
+ * bgs_gc_colsum_bwd   g = dy * (y > 0) (y NULL: no ReLU, g = dy is not written) and the per-split column sums
+ *     part_add [B, S, C] = sum_n g, part_mul [B, S, C] = sum_n g x (x NULL: not wanted).
+ * bgs_gc_channel_bwd  combines them, runs the branches backwards per image: dpre_* [B, C] (gradient of W2 a + b2),
+ *     dhz_* [B, 2, P] (gradient of W1 ctx + b1, gradient in front of the LayerNorm affine), dctx [B, C].
+ * bgs_gc_dx_bwd       dx_n = g_n mul + p_n dctx + ds_n w_mask, p_n = exp(s_n - m) / l,
+ *     ds_n = p_n (<x_n, dctx> - <ctx, dctx>); part_dw [B, S, C] = sum_n ds_n x_n, part_ds [B, S] = sum_n ds_n.
+ *     w_mask NULL ('avg'): dx_n = g_n mul + dctx / N.  mul NULL: no mul branch.
+ * bgs_gc_param_bwd    every parameter gradient as a sum over the images (dw_mask / db_mask: images, then splits) in
+ *     ascending order; host_dadd / host_dmul: host arrays of six device pointers in the order above.
+ *   BGS_ERR_INVALID_ARG: a missing pointer, a size < 1, S out of range, an unaligned map.
+ * ---------------------------------------------------------------------------------- */
+int bgs_gc_num_splits(int B, int N);
+int bgs_gc_pool_fwd(const float* x, const float* w_mask, const float* b_mask, int B, int N, int C, int S, float* s,
+                    float* part, float* part_ml, bgs_stream_t stream);
+int bgs_gc_channel_fwd(const float* part, const float* part_ml, int S, int B, int C, int P,
+                       const void* const* host_add, const void* const* host_mul, float eps, float* ctx, float* ml,
+                       float* add, float* mul, float* hn_add, float* hn_mul, float* rstd, bgs_stream_t stream);
+int bgs_gc_apply_fwd(const float* x, const float* mul, const float* add, const float* identity, int relu, int B, int N,
+                     int C, float* y, bgs_stream_t stream);
+int bgs_gc_colsum_bwd(const float* dy, const float* y, const float* x, int B, int N, int C, int S, float* g,
+                      float* part_add, float* part_mul, bgs_stream_t stream);
+int bgs_gc_channel_bwd(const float* part_add, const float* part_mul, int S, int B, int C, int P,
+                       const void* const* host_add, const void* const* host_mul, const float* mul, const float* hn_add,
+                       const float* hn_mul, const float* rstd, float* dpre_add, float* dpre_mul, float* dhz_add,
+                       float* dhz_mul, float* dctx, bgs_stream_t stream);
+int bgs_gc_dx_bwd(const float* g, const float* x, const float* s, const float* ml, const float* ctx, const float* dctx,
+                  const float* mul, const float* w_mask, int B, int N, int C, int S, float* dx, float* part_dw,
+                  float* part_ds, bgs_stream_t stream);
+int bgs_gc_param_bwd(int B, int S, int C, int P, const float* ctx, const float* dpre_add, const float* dpre_mul,
+                     const float* hn_add, const float* hn_mul, const float* dhz_add, const float* dhz_mul,
+                     const float* part_dw, const float* part_ds, void* const* host_dadd, void* const* host_dmul,
+                     float* dw_mask, float* db_mask, bgs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
